@@ -23,8 +23,9 @@ stores into mapped peer windows, device-side thresholds, no send ever waits.
     ahead) are force-completed like the reference's: the sink gets zeros with
     count 0 and the master a ``CompleteAllreduce`` for each (W:100-106);
   * ``WorkerTerminated`` marks the peer dead: it is never waited for again;
-  * ``close`` (the master's Shutdown at maxRound) retires this rank, so peers
-    stop waiting for its copies of later rounds.
+  * ``close`` (the master's Shutdown at maxRound) forces every wait, lets the
+    round thread serve what is left of the rounds the master started, and
+    retires this rank, so peers stop waiting for its copies of later rounds.
 Every handler swallows and records errors like the reference's ``tryCatch``
 (W:287-299)."""
 from __future__ import annotations
@@ -152,7 +153,10 @@ class OneSidedWorker:
             with self._cv:
                 while not self._stop and self.next_round > self.max_round and not self._joins:
                     self._cv.wait(0.5)
-                if self._stop:
+                # closing: the rounds the master started are still served (every
+                # wait is forced by then), so a worker a few rounds behind at the
+                # job's end hands its sink every round up to the last one
+                if self._stop and self.next_round > self.max_round:
                     return
                 want = self.next_round
                 joins, self._joins = self._joins, []
@@ -183,7 +187,7 @@ class OneSidedWorker:
                 log.error("%s: round %d failed: %s", self.name, want, e)
                 with self._cv:
                     if self._stop:
-                        return
+                        return  # no retries once closing
                     self._cv.wait(0.1)
 
     def _force_complete(self, r: int) -> None:

@@ -12,6 +12,12 @@ as in BASELINE config 2.
 
 algbw = buffer bytes / seconds per round; busbw = algbw * 2(N-1)/N.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times ``--steps`` rounds and prints the line.
+``--full`` adds what else this file measures and checks after the timed
+rounds: the exactness check, the RCCL comparator, the other lane, the link
+probe and the other BASELINE configs.  ``--dump-outputs DIR`` writes the last
+timed round's output as ``.npy`` files (same inputs every run).
 """
 from __future__ import annotations
 
@@ -40,10 +46,17 @@ def parse():
     p.add_argument("--compare-rccl", choices=["auto", "on", "off"], default="auto",
                    help="also time torch.distributed all_reduce (RCCL) on the same buffer after the timed "
                         "region -- auto: on for N>1")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything besides the headline: the exactness check, the "
+                        "RCCL comparator, the other lane, the link probe and the extra configs (each still has its "
+                        "own switch below).  Without it a run sets up, warms up, times --steps rounds and prints")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last timed round returned (data and count, float32) "
+                        "as DIR/<name>.npy; a fixed seeded sample of the elements when the buffer is large")
     p.add_argument("--no-check", action="store_true")
     p.add_argument("--extras", choices=["auto", "on", "off"], default="auto",
-                   help="after the headline, also time BASELINE config 3 (bf16 1 GiB) and config 5 (MLP DP-SGD) "
-                        "-- auto: only for the default headline invocation")
+                   help="with --full: after the headline, also time BASELINE config 3 (bf16 1 GiB) and config 5 "
+                        "(MLP DP-SGD) -- auto: only for the default headline invocation")
     p.add_argument("--watchdog-s", type=float, default=900.0,
                    help="dump stacks and exit if the run is not done after this many seconds (0: off)")
     p.add_argument("--phase-deadline-s", type=float, default=180.0,
@@ -130,6 +143,32 @@ def timed(step, steps: int, warmup: int, world: int, barrier) -> float:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_MAX_ELEMS = 1 << 22  # per array: 16 MiB of float32, data + count stay far below 64 MB
+
+
+def dump_outputs(path: str, out, max_elems: int = DUMP_MAX_ELEMS) -> dict:
+    """Write what a caller of the timed path received from its last round
+    (AllReduceOutput.data and .count) as ``path/data.npy`` and
+    ``path/count.npy``, float32.  Up to DUMP_MAX_ELEMS elements are written
+    whole; of a larger output the same seeded sample of elements every run
+    (sorted indices from a CPU generator, seed 0), so two builds run with the
+    same arguments can be compared file by file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    data, count = out.data, out.count
+    n = data.numel()
+    if n > max_elems:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, n, (max_elems,), generator=g).sort().values.to(data.device)
+        data, count = data.index_select(0, idx), count.index_select(0, idx)
+    arrays = {"data": data, "count": count}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    return {"dir": path, "arrays": sorted(arrays), "elements": int(data.numel()), "of": int(n)}
 
 
 class _Skip(Exception):
@@ -713,6 +752,11 @@ def _identity(ar, dev) -> dict:
 
 def main() -> int:
     args = parse()
+    if not args.full:
+        # a plain run measures the headline only; whatever else this file
+        # measures or checks after the timed rounds needs --full
+        args.no_check = True
+        args.compare_rccl = args.link_probe = args.extras = "off"
     if args.transport == "reactive":
         # one stream per peer: must not share hardware queues (read at HIP init)
         os.environ["GPU_MAX_HW_QUEUES"] = "32"
@@ -1000,12 +1044,25 @@ def main() -> int:
             t = torch.tensor([dt, host_s], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt, host_s = float(t[0].item()), float(t[1].item())
-        return dt, host_s
+        return dt, host_s, out
 
-    dt, host_s = guard.run("timed", max(dl, args.steps * 2.0), timed_region)
+    dt, host_s, last_out = guard.run("timed", max(dl, args.steps * 2.0), timed_region)
     ms = dt / args.steps * 1e3
     algbw = nbytes / (dt / args.steps) / 1e9
     busbw = algbw * (2 * (world - 1) / world) if world > 1 else None
+
+    # The last timed round's output, before any later round reuses its buffer
+    # (rank 0's copy: with exact thresholds every rank receives the same; the
+    # peers wait, so none of them starts a round into rank 0's window row).
+    dumped = None
+    if args.dump_outputs:
+        def dump():
+            d = dump_outputs(args.dump_outputs, last_out) if rank == 0 else None
+            _sync()
+            barrier()
+            return d
+
+        dumped = guard.run("dump_outputs", dl, dump)
 
     # Exactness after the timed rounds (untimed).
     ok = None
@@ -1053,7 +1110,7 @@ def main() -> int:
         used = chosen_lane or ("ipc" if args.data_plane == "ipc" else "collective" if coll > steps_p2p else "p2p")
         if world == 1:
             return "local", None
-        if args.data_plane == "ipc" or ipc_only:
+        if not args.full or args.data_plane == "ipc" or ipc_only:
             return used, None
         if ar.transport != "stream":
             return used, None
@@ -1125,6 +1182,8 @@ def main() -> int:
         "output": ("the lane's window row, valid until the next round (no copy into a caller buffer)"
                    if lane_output else "fresh tensor per round" if args.fresh_out else "preallocated, reused"),
     })
+    if dumped:
+        line["dumped_outputs"] = dumped
     if rccl_err:
         line["rccl_compare_error"] = rccl_err
     if rccl_fallback:

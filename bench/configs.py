@@ -16,8 +16,9 @@ communicators, event-polled arrivals): with thresholds 0.75 the fast ranks
 complete rounds without waiting for the straggler.  On the scheduled
 transport every rank still exchanges every chunk (RCCL p2p is a rendezvous),
 so a straggler delays everyone and the thresholds only decide which
-contributions are summed.  ``bench.py`` (default invocation) also times
-configs 3 and 5 after the headline and reports them under ``extra_configs``.
+contributions are summed.  ``bench.py --full`` (otherwise default arguments)
+also times configs 3 and 5 after the headline and reports them under
+``extra_configs``.
 """
 from __future__ import annotations
 

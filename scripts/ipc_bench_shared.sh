@@ -11,7 +11,7 @@ mkdir -p gpurun_out/bench_shared
 run() {  # run <n> <tag> <extra args...>
   local n=$1 tag=$2; shift 2
   AKKA_SHARE_GPU=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$n \
-    --master-addr 127.0.0.1 --master-port $((29600 + n + ${#tag})) bench.py --gpus $n --steps 20 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port $((29600 + n + ${#tag})) bench.py --gpus $n --full --steps 20 --warmup 5 \
     --compare-rccl off "$@" > gpurun_out/bench_shared/$tag.json 2> gpurun_out/bench_shared/$tag.err \
     || { echo "$tag rc=$?"; tail -20 gpurun_out/bench_shared/$tag.err; return 1; }
   cat gpurun_out/bench_shared/$tag.json

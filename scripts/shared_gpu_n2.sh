@@ -7,7 +7,7 @@ O=gpurun_out/sharedgpu
 mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0 AKKA_SHARE_GPU=1 NCCL_DEBUG=WARN
 timeout -k 10 150 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full --steps 5 --warmup 2 \
   --compare-rccl off --extras off --watchdog-s 120 > $O/n2.json 2> $O/n2.err
 rc=$?
 echo "rc=$rc"

@@ -16,7 +16,7 @@ def test_bench_prints_one_baseline_line():
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         baseline = json.load(f)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
-                        "--size-mb", "16", "--extras", "on"],
+                        "--size-mb", "16", "--full", "--extras", "on"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -35,10 +35,38 @@ def test_bench_prints_one_baseline_line():
     assert ex["cfg5_mlp_dp_sgd_bf16_graph"]["steps_per_s"] > 0, ex
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full the run ends after the timed rounds (no check, no extra
+    configs).  --dump-outputs writes the last timed round's output: at N=1
+    the seeded input itself with every count 1; 32 MiB is above the element
+    cap, so the files hold the fixed seeded sample."""
+    import numpy as np
+    import torch
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--size-mb", "32", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "fp32"
+    assert abs(d["value"] - d["config"]["buffer_bytes"] / (d["ms_per_step"] * 1e-3) / 1e9) / d["value"] < 0.05
+    assert d["exact"] is None and "extra_configs" not in d and "extras_error" not in d
+    S = (32 << 20) // 4
+    k = d["dumped_outputs"]["elements"]
+    assert d["dumped_outputs"]["of"] == S and k < S and 2 * 4 * k <= 64e6
+    data, count = np.load(tmp_path / "out" / "data.npy"), np.load(tmp_path / "out" / "count.npy")
+    assert data.dtype == np.float32 and count.dtype == np.float32 and data.shape == count.shape == (k,)
+    x = torch.randn(S, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1234)).cpu()
+    idx = torch.randint(0, S, (k,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(data, x[idx].numpy()) and np.all(count == 1)
+
+
 def test_bench_extras_deadline_keeps_headline():
     """Extras that overrun their deadline are dropped; the headline line still prints once, rc 0."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
-                        "--size-mb", "16", "--extras", "on", "--extras-deadline-s", "0.01"],
+                        "--size-mb", "16", "--full", "--extras", "on", "--extras-deadline-s", "0.01"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -67,7 +95,7 @@ def test_bench_multirank_on_one_card(plane):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", str(n), "--steps", "4", "--warmup", "2", "--size-mb", "16", "--data-plane", plane,
-                        "--compare-rccl", "off", *extra],
+                        "--full", "--compare-rccl", "off", *extra],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -119,7 +147,7 @@ def test_bench_rccl_init_failure_falls_back_to_ipc():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "1", "--size-mb", "16", "--compare-rccl", "off",
-                        "--extras", "off"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+                        "--full", "--extras", "off"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -145,7 +173,7 @@ def test_bench_preflight_failure_falls_back_to_ipc():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "1", "--size-mb", "16", "--data-plane", "ipc_p2p",
-                        "--extras", "off", "--link-probe", "off"], capture_output=True, text=True, timeout=300,
+                        "--full", "--extras", "off", "--link-probe", "off"], capture_output=True, text=True, timeout=300,
                        cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -175,7 +203,7 @@ def test_bench_cfg5_two_ranks_on_one_card():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "3", "--warmup", "1", "--size-mb", "16", "--data-plane", "ipc",
-                        "--extras", "on", "--extras-only", "cfg5", "--link-probe", "off", "--compare-rccl", "off",
+                        "--full", "--extras", "on", "--extras-only", "cfg5", "--link-probe", "off", "--compare-rccl", "off",
                         "--extras-deadline-s", "150"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

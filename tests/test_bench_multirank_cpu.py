@@ -21,11 +21,11 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
-def _run(n, *extra, env=None, expect_rc=0):
+def _run(n, *extra, env=None, expect_rc=0, full=True):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(n), "--steps", "3", "--warmup", "1", "--size-mb", "0.5", "--chunk-mb", "0.0625",
-           "--device", "cpu", *extra]
+           "--device", "cpu", *(["--full"] if full else []), *extra]
     e = dict(os.environ)
     e.update(env or {})
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=e)
@@ -67,6 +67,53 @@ def test_bench_multirank_line(n, transport):
     assert len(lp["all_peers_push_GBps_per_rank"]) == n and "not a link measurement" in lp["note"]
     if transport == "stream":
         assert d["other_lane"]["lane"] == "collective" and d["other_lane"]["algbw_GBps"] > 0
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full: set-up, warm-up, the timed rounds, the line -- no
+    check, comparator, other lane, link probe or extra configs.
+    --dump-outputs writes what the last timed round returned: the sum of the
+    ranks' seeded inputs (two fp32 terms: exact), every count N."""
+    import numpy as np
+    import torch
+
+    d = _run(2, "--dump-outputs", str(tmp_path / "out"), full=False)
+    assert d["value"] > 0 and d["steps"] == 3 and d["unit"] == "GB/s" and d["dtype"] == "fp32"
+    assert abs(d["value"] - d["config"]["buffer_bytes"] / (d["ms_per_step"] * 1e-3) / 1e9) / d["value"] < 0.05
+    assert d["exact"] is None and d["other_lane"] is None and d["rccl_allreduce_algbw_GBps"] is None
+    assert "link_probe" not in d and "extra_configs" not in d and "extras_error" not in d
+    S = d["config"]["buffer_bytes"] // 4
+    assert d["dumped_outputs"]["arrays"] == ["count", "data"] and d["dumped_outputs"]["elements"] == S
+    data, count = np.load(tmp_path / "out" / "data.npy"), np.load(tmp_path / "out" / "count.npy")
+    assert data.dtype == np.float32 and count.dtype == np.float32 and data.shape == count.shape == (S,)
+    want = sum(torch.randn(S, generator=torch.Generator().manual_seed(1234 + r)) for r in range(2))
+    assert np.array_equal(data, want.numpy()) and np.all(count == 2)
+
+
+def test_bench_dump_samples_a_large_output(tmp_path):
+    """An output above the element cap is written as a fixed seeded sample:
+    the same sorted indices on every call, values taken from them."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    from akka_allreduce_amd.data import AllReduceOutput
+
+    spec = importlib.util.spec_from_file_location("bench_py", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    n = 10007
+    out = AllReduceOutput(torch.arange(n, dtype=torch.float32), count=torch.full((n,), 3, dtype=torch.int32))
+    info = bench.dump_outputs(str(tmp_path / "a"), out, max_elems=1000)
+    bench.dump_outputs(str(tmp_path / "b"), out, max_elems=1000)
+    a = np.load(tmp_path / "a" / "data.npy")
+    assert info["elements"] == 1000 and info["of"] == n and a.shape == (1000,) and a.dtype == np.float32
+    assert np.all(np.diff(a) >= 0) and a.min() >= 0 and a.max() < n and len(np.unique(a)) > 900
+    assert np.array_equal(a, np.load(tmp_path / "b" / "data.npy"))
+    assert np.all(np.load(tmp_path / "a" / "count.npy") == 3)
+    assert bench.DUMP_MAX_ELEMS * 4 * 2 <= 64e6  # data + count, float32
 
 
 def test_bench_collective_lane_line():

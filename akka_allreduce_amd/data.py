@@ -133,10 +133,11 @@ class AllReduceOutput:
                 self._count = self.geometry.expand_counts(self.counts_per_chunk)
         return self._count
 
-    def _fused_ok(self, dst: torch.Tensor) -> bool:
+    def _fused_ok(self, dst: torch.Tensor, wide: bool = False) -> bool:
         d, g = self.data, self.geometry
+        dt_ok = (d.dtype == torch.bfloat16 and dst.dtype == torch.float32) if wide else dst.dtype == d.dtype
         return (d.is_cuda and d.dtype in (torch.float32, torch.bfloat16) and self.counts_per_chunk is not None
-                and g is not None and self._count is None and dst.is_contiguous() and dst.dtype == d.dtype
+                and g is not None and self._count is None and dst.is_contiguous() and dt_ok
                 and dst.device == d.device and dst.numel() == d.numel() and d.data_ptr() % 16 == 0
                 and dst.data_ptr() % 16 == 0)
 
@@ -145,36 +146,61 @@ class AllReduceOutput:
 
         d, g = self.data, self.geometry
         pc = self.counts_per_chunk.contiguous()
+        name = {torch.bfloat16: "bfloat16", torch.float32: "float32"}
         load().count_mean(dst.data_ptr(), d.data_ptr(), pc.data_ptr(), g.dataSize, g.step, g.workerNum,
-                          g.maxChunkSize, g.kmax, "bfloat16" if d.dtype == torch.bfloat16 else "float32",
+                          g.maxChunkSize, g.kmax, name[dst.dtype],
                           torch.cuda.current_stream(d.device).cuda_stream, axpy, float(alpha),
-                          shadow.data_ptr() if shadow is not None else 0)
+                          shadow.data_ptr() if shadow is not None else 0, name[d.dtype])
 
-    def axpy_mean_(self, y: torch.Tensor, alpha: float, shadow: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _is_wide(self, dst_dtype: torch.dtype) -> bool:
+        return self.data.dtype == torch.bfloat16 and dst_dtype == torch.float32
+
+    def axpy_mean_(self, y: torch.Tensor, alpha: float, shadow: Optional[torch.Tensor] = None, *,
+                   wide: bool = False) -> torch.Tensor:
         """``y += alpha * mean()`` in one fused pass on the GPU (the SGD update
         of a flat parameter buffer: alpha = -lr); ``y`` is updated in place.
         ``shadow`` (bf16, same length as fp32 ``y``) also receives the updated
-        values, stored by the same pass (a separate cast off the fused path)."""
+        values, stored by the same pass (a separate cast off the fused path).
+        ``wide=True`` with fp32 ``y`` and a bf16 sum (a compressed wire) uses
+        the fp32 mean of the sum, not its bf16 rounding: the same single pass
+        on the GPU, reading bf16 and writing fp32."""
         self.wait()
-        if self._fused_ok(y) and (shadow is None or (
+        wide = wide and self._is_wide(y.dtype)
+        if self._fused_ok(y, wide) and (shadow is None or (
                 y.dtype == torch.float32 and shadow.dtype == torch.bfloat16 and shadow.is_contiguous()
                 and shadow.numel() == y.numel() and shadow.device == y.device and shadow.data_ptr() % 16 == 0)):
             self._count_mean(y, True, alpha, shadow)
             return y
-        y.add_(self.mean().view_as(y).to(y.dtype), alpha=alpha)
+        m = self.mean(dtype=torch.float32) if wide else self.mean()
+        y.add_(m.view_as(y).to(y.dtype), alpha=alpha)
         if shadow is not None:
             shadow.copy_(y.view_as(shadow))
         return y
 
-    def mean(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def mean(self, out: Optional[torch.Tensor] = None, *, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """Element-wise average over the contributors that made it (0 where none).
 
         On the GPU this is one fused pass (``count_mean`` kernel: each element
         divided by its chunk's count from the tiny per-chunk table) instead of
         expanding per-element counts; ``out`` may be any same-shape tensor,
-        including the buffer that was reduced (gradient buckets)."""
+        including the buffer that was reduced (gradient buckets).
+        ``dtype=torch.float32`` on a bf16 sum gives the fp32 mean (the division
+        in fp32, no second rounding to bf16), into an fp32 ``out`` if given."""
         self.wait()
         d = self.data
+        if dtype is not None and dtype != d.dtype:
+            if not self._is_wide(dtype):
+                raise ValueError(f"mean: dtype={dtype} from {d.dtype} data (only float32 from bfloat16)")
+            if out is not None and out.dtype != dtype:
+                raise ValueError(f"mean: out must be {dtype}")
+            dst = torch.empty(d.shape, dtype=dtype, device=d.device) if out is None else out
+            if self._fused_ok(dst, True):
+                self._count_mean(dst, False, 0.0)
+                return dst
+            c = self.count.to(dtype)
+            m = torch.where(c > 0, d.to(dtype) / c.clamp(min=1), torch.zeros_like(c))
+            dst.copy_(m.view_as(dst))
+            return dst
         if d.is_cuda:
             dst = torch.empty_like(d) if out is None else out
             if self._fused_ok(dst):

@@ -246,7 +246,9 @@ class GraphedDPStep:
         if self.allreduce is not None and lr is None:
             raise ValueError("GraphedDPStep: a captured update needs its learning rate")
         self.lr = lr
-        self._out = torch.empty_like(bucket.flat) if self.allreduce is not None else None
+        # the round's output buffer: the wire's dtype with a compressed bucket
+        self._out = torch.empty_like(bucket.wire if bucket.wire is not None else bucket.flat) \
+            if self.allreduce is not None else None
         self.replays = 0
 
         def fb():
@@ -264,6 +266,8 @@ class GraphedDPStep:
         # a captured update changes the parameters in the warmup steps: they
         # are put back afterwards (the warmup's rounds still ran on every rank)
         snap = bucket.pflat.clone() if self.allreduce is not None else None
+        # ... and so is a compressed bucket's error-feedback residual
+        rsnap = bucket.residual.clone() if (self.allreduce is not None and bucket.residual is not None) else None
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 fb()
@@ -280,6 +284,8 @@ class GraphedDPStep:
             if bucket.sflat is not None:
                 bucket.sflat.copy_(bucket.pflat)
             bucket._shadow_versions = [p._version for p in bucket.params]
+        if rsnap is not None:
+            bucket.residual.copy_(rsnap)
         self._ptrs = self._pointers()  # the shadow exists now
 
     def static_inputs(self):
@@ -290,13 +296,15 @@ class GraphedDPStep:
     def _pointers(self):
         b = self.bucket
         return (b.flat.data_ptr(), b.pflat.data_ptr(), b.sflat.data_ptr() if b.sflat is not None else 0,
-                [p.data_ptr() for p in b.params], [p.grad.data_ptr() if p.grad is not None else 0 for p in b.params])
+                [p.data_ptr() for p in b.params], [p.grad.data_ptr() if p.grad is not None else 0 for p in b.params],
+                b.wire.data_ptr() if b.wire is not None else 0, b.residual.data_ptr() if b.residual is not None else 0)
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, lr: float, allreduce: Optional[AllreduceFn],
                  sync_loss: bool = False):
         b = self.bucket
         if self._pointers() != self._ptrs:
-            raise RuntimeError("GraphedDPStep: a parameter, gradient or shadow buffer moved since the capture")
+            raise RuntimeError("GraphedDPStep: a parameter, gradient, shadow, wire or residual buffer moved "
+                               "since the capture")
         if b.use_shadow(self.lowp) != (self.lowp is not None and b.sflat is not None):
             raise RuntimeError("GraphedDPStep: the bf16 shadow is no longer usable")
         if x.data_ptr() != self.sx.data_ptr():

@@ -1,6 +1,7 @@
 """Device ops backed by the gfx950 kernels in ``csrc/kernels/kernels.hip``."""
 from .colsum import colsum
+from .compress import pack_bf16
 from .reduce import chunk_reduce, count_expand
 from .xent import cross_entropy
 
-__all__ = ["chunk_reduce", "colsum", "count_expand", "cross_entropy"]
+__all__ = ["chunk_reduce", "colsum", "count_expand", "cross_entropy", "pack_bf16"]

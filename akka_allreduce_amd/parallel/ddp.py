@@ -49,12 +49,29 @@ class ThresholdHookState:
     enough (``ipc_capacity``: the window is sized for ``bucket_cap_mb``).
     Reactive engines keep one transport each (their phase-2 groups are issued
     in a timing-dependent order, which two engines must not interleave on one
-    pair communicator)."""
+    pair communicator).
+
+    ``wire_dtype=torch.bfloat16``: fp32 buckets travel as bf16
+    (``ops.pack_bf16``; with ``error_feedback`` one fp32 residual per bucket
+    index carries this rank's rounding error into the next step) and the fp32
+    mean is read straight from the bf16 sum.  Buckets that are already bf16
+    ignore it.  Not with ``transport="reactive"``, whose rounds may complete
+    while a send of the (reused) wire buffer is still in flight."""
 
     def __init__(self, *, th_reduce: float = 1.0, th_complete: float = 1.0, max_lag: int = 2,
                  max_chunk_size: int = 1 << 20, transport: str = "stream", broadcast_lag: int = 2,
                  async_op: bool = True, th_allreduce=None, data_plane: str = "rccl", tune: bool = False,
-                 bucket_cap_mb: float = 25.0, onesided_options: Optional[dict] = None):
+                 bucket_cap_mb: float = 25.0, onesided_options: Optional[dict] = None,
+                 wire_dtype: Optional[torch.dtype] = None, error_feedback: bool = True):
+        if wire_dtype is not None and wire_dtype != torch.bfloat16:
+            raise ValueError(f"wire_dtype={wire_dtype}: only torch.bfloat16")
+        if wire_dtype is not None and transport == "reactive":
+            raise ValueError("wire_dtype needs a transport that is done with its input when the round completes "
+                             "(not 'reactive')")
+        self.wire_dtype = wire_dtype
+        self.error_feedback = error_feedback
+        # bucket.index() -> (wire, residual or None)
+        self.wire_bufs: Dict[int, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
         self.kw = dict(th_reduce=th_reduce, th_complete=th_complete, max_lag=max_lag, max_chunk_size=max_chunk_size,
                        transport=transport, broadcast_lag=broadcast_lag, th_allreduce=th_allreduce,
                        data_plane=data_plane, onesided_options=onesided_options)
@@ -91,6 +108,17 @@ class ThresholdHookState:
             self.engines[key] = ar
         return ar
 
+    def wire_for(self, index: int, flat: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """The wire buffer and residual of DDP bucket ``index`` (created on
+        first use; DDP's one bucket rebuild after the first step changes the
+        sizes, which starts them afresh)."""
+        bufs = self.wire_bufs.get(index)
+        if bufs is None or bufs[0].numel() != flat.numel() or bufs[0].device != flat.device:
+            wire = torch.empty(flat.numel(), dtype=self.wire_dtype, device=flat.device)
+            res = torch.zeros(flat.numel(), dtype=torch.float32, device=flat.device) if self.error_feedback else None
+            bufs = self.wire_bufs[index] = (wire, res)
+        return bufs
+
     def transports(self) -> int:
         """Distinct transports (communicators) the hook's engines use."""
         return len({ar.worker._core.transport_id() for ar in self.engines.values() if ar.worker is not None})
@@ -104,6 +132,15 @@ def threshold_allreduce_hook(state: ThresholdHookState, bucket: dist.GradBucket)
         work = flat.float()
     else:
         work = flat
+    wired = state.wire_dtype is not None and flat.dtype == torch.float32 and t.is_contiguous()
+    if wired:
+        from ..ops.compress import pack_bf16
+
+        # Reusing the per-bucket wire buffer is safe: DDP consumes the future,
+        # whose event follows the mean and therefore the round that read the
+        # wire, before the next backward reaches this pack again.
+        work, res = state.wire_for(bucket.index(), flat)
+        pack_bf16(flat, res, out=work)  # on the current stream, which the round is ordered behind
     ar = state.engine(work)
     cuda = work.is_cuda
     async_op = bool(state.async_op and cuda and ar.runs_async())
@@ -112,7 +149,8 @@ def threshold_allreduce_hook(state: ThresholdHookState, bucket: dist.GradBucket)
     state.async_rounds += int(async_op)
     if not cuda:
         fut: torch.futures.Future[torch.Tensor] = torch.futures.Future()
-        fut.set_result(out.mean().to(t.dtype).view_as(t))
+        fut.set_result(out.mean(out=flat, dtype=flat.dtype).view_as(t) if wired
+                       else out.mean().to(t.dtype).view_as(t))
         return fut
     # CUDA-aware future: set_result records an event on the stream current at
     # that point, and DDP's wait() makes ITS stream wait on that event (and
@@ -121,7 +159,10 @@ def threshold_allreduce_hook(state: ThresholdHookState, bucket: dist.GradBucket)
     # the backward pass -- only waits where DDP consumes the bucket.
     side = ar.async_stream() if async_op else torch.cuda.current_stream(work.device)
     with torch.cuda.stream(side):
-        if work is flat and t.is_contiguous() and ar.transport != "reactive":
+        if wired:
+            # bf16 sum -> fp32 mean straight into the bucket, one pass
+            mean = out.mean(out=flat, dtype=flat.dtype).view_as(t)
+        elif work is flat and t.is_contiguous() and ar.transport != "reactive":
             # the mean straight into the bucket (the round is done with its
             # input by then, in this stream's order): no allocation, and the
             # result aliases the bucket, so DDP's copy of it into the

@@ -23,17 +23,37 @@ AllreduceFn = Callable[[torch.Tensor], AllReduceOutput]
 class GradientBucket:
     """``flatten_params=True`` also moves the parameters into one flat buffer
     with the gradients' layout, so the SGD update fuses into the averaging
-    (``sgd_from``: one pass ``p -= lr * sum / count`` on the GPU)."""
+    (``sgd_from``: one pass ``p -= lr * sum / count`` on the GPU).
+
+    ``wire_dtype=torch.bfloat16`` (fp32 gradients only) halves the bytes a
+    round moves: ``average`` / ``sgd_from`` pack ``flat`` into the bf16
+    ``wire`` buffer (``ops.pack_bf16``), the allreduce -- built with
+    ``dtype=torch.bfloat16`` -- runs on ``wire``, and the bf16 sum is read
+    straight into fp32 (``flat``, or the fused update of ``pflat``).  With
+    ``error_feedback`` the fp32 ``residual`` carries what this rank's rounding
+    dropped into its next step's gradient.  It does not make up for a
+    contribution that a threshold round left out, nor for the owner's single
+    rounding of the fp32 sum to bf16."""
 
     def __init__(self, params: List[torch.nn.Parameter], dtype: Optional[torch.dtype] = None,
-                 flatten_params: bool = False):
+                 flatten_params: bool = False, wire_dtype: Optional[torch.dtype] = None,
+                 error_feedback: bool = True):
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no trainable parameters")
         dev = self.params[0].device
         dt = dtype or self.params[0].dtype
         self.numel = sum(p.numel() for p in self.params)
+        if wire_dtype is not None and (wire_dtype != torch.bfloat16 or dt != torch.float32):
+            raise ValueError(f"wire_dtype={wire_dtype} with {dt} gradients: only bfloat16 for float32 gradients")
         self.flat = torch.zeros(self.numel, dtype=dt, device=dev)
+        self.wire_dtype = wire_dtype
+        self.wire: Optional[torch.Tensor] = None
+        self.residual: Optional[torch.Tensor] = None
+        if wire_dtype is not None:
+            self.wire = torch.empty(self.numel, dtype=wire_dtype, device=dev)
+            if error_feedback:
+                self.residual = torch.zeros(self.numel, dtype=dt, device=dev)
         self.pflat: Optional[torch.Tensor] = None
         # low-precision copy of pflat kept current by the fused update (use_shadow)
         self.sflat: Optional[torch.Tensor] = None
@@ -151,10 +171,33 @@ class GradientBucket:
         """flat <- mean over contributors (no-op without an allreduce)."""
         if allreduce is None:
             return None
+        if self.wire is not None:
+            out = self._wire_round(allreduce, None)
+            out.mean(out=self.flat, dtype=self.flat.dtype)
+            return out
         out = allreduce(self.flat)
         self.average_out(out)  # one fused pass on the GPU, straight into the bucket
         return out
 
+    def reset_residual(self) -> None:
+        """Zero the error-feedback residual.  It holds rounding error of
+        gradients scaled for the run so far: call this when the learning-rate
+        regime changes abruptly, or after loading a checkpoint (parameters
+        the residual was not accumulated against)."""
+        if self.residual is not None:
+            self.residual.zero_()
+
+    def _wire_round(self, allreduce: AllreduceFn, out_buf: Optional[torch.Tensor]) -> AllReduceOutput:
+        from ..ops.compress import pack_bf16
+
+        if out_buf is not None and out_buf.dtype != self.wire_dtype:
+            raise ValueError(f"out_buf must be {self.wire_dtype} with a compressed wire")
+        pack_bf16(self.flat, self.residual, out=self.wire)
+        out = allreduce(self.wire) if out_buf is None else allreduce(self.wire, out=out_buf)
+        if out.data.dtype != self.wire_dtype:
+            raise RuntimeError(f"the allreduce returned {out.data.dtype} for a {self.wire_dtype} wire: "
+                               "build the engine with dtype=torch.bfloat16")
+        return out
 
     def sgd_from(self, allreduce: Optional[AllreduceFn], lr: float,
                  out_buf: Optional[torch.Tensor] = None) -> Optional[AllReduceOutput]:
@@ -165,6 +208,17 @@ class GradientBucket:
         if allreduce is None:
             sgd_step(self.params, lr)
             return None
+        if self.wire is not None:
+            out = self._wire_round(allreduce, out_buf)
+            if self.pflat is not None:
+                # bf16 sum -> fp32 parameters (and the bf16 shadow): the same single pass
+                out.axpy_mean_(self.pflat, -lr, shadow=self.sflat if self._shadow_on else None, wide=True)
+            else:
+                out.mean(out=self.flat, dtype=self.flat.dtype)
+                sgd_step(self.params, lr)
+            if self._shadow_on:
+                self._shadow_versions = [p._version for p in self.params]
+            return out
         out = allreduce(self.flat) if out_buf is None else allreduce(self.flat, out=out_buf)
         if self.pflat is not None and out.data.dtype == self.pflat.dtype:
             out.axpy_mean_(self.pflat, -lr, shadow=self.sflat if self._shadow_on else None)

@@ -413,7 +413,7 @@ class WorkerCore final : public EngineHost {
     AKKA_CHECK(dev_ && !dev_->is_host(), "count_mean: device path only");
     launch_count_mean(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<void*>(dst),
                       reinterpret_cast<const void*>(src), reinterpret_cast<const int32_t*>(counts), g.S, g.step, g.N,
-                      g.C, dp_->kmax(), dt_);
+                      g.C, dp_->kmax(), dt_, dt_);
   }
   void expand_counts(uintptr_t out, uintptr_t counts, uintptr_t stream) {
     const Geometry& g = engine_->geometry();
@@ -1070,13 +1070,21 @@ PYBIND11_MODULE(_native, m) {
   });
   m.def("count_mean", [](uintptr_t dst, uintptr_t src, uintptr_t counts, int64_t S, int64_t step, int32_t N,
                          int64_t C, int32_t kmax, std::string dtype, uintptr_t stream, bool axpy, float alpha,
-                         uintptr_t shadow) {
+                         uintptr_t shadow, std::string src_dtype) {
+    const DType dt = dtype == "bfloat16" ? DType::BF16 : DType::F32;
+    // src_dtype "": the source has the destination's dtype
+    const DType sdt = src_dtype.empty() ? dt : (src_dtype == "bfloat16" ? DType::BF16 : DType::F32);
     launch_count_mean(as_stream(stream), reinterpret_cast<void*>(dst), reinterpret_cast<const void*>(src),
-                      reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax,
-                      dtype == "bfloat16" ? DType::BF16 : DType::F32, axpy, alpha, reinterpret_cast<void*>(shadow));
+                      reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax, dt, sdt, axpy, alpha,
+                      reinterpret_cast<void*>(shadow));
   }, py::arg("dst"), py::arg("src"), py::arg("counts"), py::arg("S"), py::arg("step"), py::arg("N"), py::arg("C"),
      py::arg("kmax"), py::arg("dtype"), py::arg("stream"), py::arg("axpy") = false, py::arg("alpha") = 0.f,
-     py::arg("shadow") = 0);
+     py::arg("shadow") = 0, py::arg("src_dtype") = "");
+  m.def("pack_bf16", [](uintptr_t dst, uintptr_t src, uintptr_t residual, int64_t n, uintptr_t stream) {
+    AKKA_CHECK(n >= 0 && (n == 0 || (dst != 0 && src != 0)), "pack_bf16: null buffer");
+    launch_pack_bf16(as_stream(stream), reinterpret_cast<void*>(dst), reinterpret_cast<const float*>(src),
+                     reinterpret_cast<float*>(residual), n);
+  }, py::arg("dst"), py::arg("src"), py::arg("residual"), py::arg("n"), py::arg("stream") = 0);
   m.def("colsum_bf16", [](uintptr_t out, uintptr_t in, int64_t M, int64_t ncol, uintptr_t part, uintptr_t tickets,
                           int32_t splits, uintptr_t stream, bool lite, uintptr_t act, uintptr_t gout) {
     launch_colsum_bf16(as_stream(stream), reinterpret_cast<float*>(out), reinterpret_cast<const void*>(in), M, ncol,

@@ -24,10 +24,15 @@ void launch_reduce(hipStream_t s, const ReduceSpec& spec, DType dt, ReduceImpl i
 void launch_count_expand(hipStream_t s, int32_t* out, const int32_t* counts, int64_t S, int64_t step, int32_t N,
                          int64_t C, int32_t kmax);
 // dst = src / per-chunk count (0 where the count is 0), one pass; with
-// `axpy`: dst += alpha * that mean (fused SGD update).
+// `axpy`: dst += alpha * that mean (fused SGD update).  dt is the
+// destination's dtype, src_dt the source's: the same, or bf16 into fp32 (the
+// sum of a compressed wire read straight into fp32 gradients / parameters).
 void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t* counts, int64_t S, int64_t step,
-                       int32_t N, int64_t C, int32_t kmax, DType dt, bool axpy = false, float alpha = 0.f,
-                       void* shadow = nullptr);
+                       int32_t N, int64_t C, int32_t kmax, DType dt, DType src_dt, bool axpy = false,
+                       float alpha = 0.f, void* shadow = nullptr);
+// q (bf16) = rne(g + r), r = (g + r) - float(q) in place; r may be null (a
+// plain cast).  r becomes 0 where the sum or its rounding is not finite.
+void launch_pack_bf16(hipStream_t s, void* q, const float* g, float* r, int64_t n);
 // out[c] = sum_r in[r, c] (bf16 [M, ncol] row-major, fp32 out): the bias
 // gradient.  part: fp32 [splits, ncol] workspace; tickets: uint32
 // [ceil(ncol / 512)] zeroed once (each launch leaves them zero again).

@@ -303,13 +303,22 @@ __global__ __launch_bounds__(kBlock) void count_expand_kernel(int32_t* __restric
 // each element is read before the same thread writes it, so no __restrict__.
 constexpr int kCmUnroll = 4;
 
-template <typename T, bool AXPY, bool SHADOW>
-__global__ __launch_bounds__(kBlock) void count_mean_kernel(T* dst, const T* src,
+// TS is the source's element type, TD the destination's.  TD == TS for the
+// plain passes; TD = float, TS = bf16 reads a bf16 sum (compressed wire) into
+// fp32 parameters.  A vector unit is one 16-B source vector: E = 8 bf16 against
+// two fp32 destination vectors in the mixed pass, so every stream keeps 16-B
+// accesses.  The per-element arithmetic is shared, so a source that is exact
+// in bf16 gives the same bits through either source type.
+template <typename TD, typename TS, bool AXPY, bool SHADOW>
+__global__ __launch_bounds__(kBlock) void count_mean_kernel(TD* dst, const TS* src,
                                                             const int32_t* __restrict__ counts, int64_t S,
                                                             int64_t step, int32_t N, int64_t C, int32_t kmax,
                                                             float alpha, unsigned short* __restrict__ shadow) {
-  static_assert(!SHADOW || (AXPY && std::is_same_v<T, float>), "shadow: fp32 SGD update only");
-  constexpr int E = VecTraits<T>::kElems;
+  static_assert(!SHADOW || (AXPY && std::is_same_v<TD, float>), "shadow: fp32 SGD update only");
+  constexpr int E = VecTraits<TS>::kElems;   // elements per unit
+  constexpr int ED = VecTraits<TD>::kElems;  // elements per destination vector
+  constexpr int ND = E / ED;                 // destination vectors per unit
+  static_assert(ND >= 1 && ND * ED == E, "the source type is never wider than the destination's");
   const int64_t nregions = int64_t(N) * kmax;
   for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
     const int32_t j = int32_t(reg / kmax);
@@ -321,13 +330,13 @@ __global__ __launch_bounds__(kBlock) void count_mean_kernel(T* dst, const T* src
     const int64_t e = s + C < be ? s + C : be;
     const int32_t v = counts[reg];
     const float fv = float(v);
-    int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first 16-B aligned element
+    int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first element 16-B aligned in every stream
     if (a > e) a = e;
     const int64_t nv = (e - a) / E;
     auto one = [&](int64_t i) {
       const float m = v > 0 ? to_f(src[i]) / fv : 0.f;
       const float r = AXPY ? to_f(dst[i]) + alpha * m : m;
-      dst[i] = from_f<T>(r);
+      dst[i] = from_f<TD>(r);
       if constexpr (SHADOW) shadow[i] = from_f<unsigned short>(r);
     };
     if (blockIdx.y == 0) {
@@ -336,42 +345,155 @@ __global__ __launch_bounds__(kBlock) void count_mean_kernel(T* dst, const T* src
     }
     const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
     v4u* d4 = reinterpret_cast<v4u*>(dst + a);
-    uint2* h2 = SHADOW ? reinterpret_cast<uint2*>(shadow + a) : nullptr;  // 4 bf16 per fp32 vector
-    auto mean_vec = [&](const v4u& sv, const v4u& dv, int64_t at) {
+    struct DVec {
+      v4u v[ND];
+    };
+    auto load_d = [&](int64_t at) {
+      DVec d;
+#pragma unroll
+      for (int k2 = 0; k2 < ND; ++k2) d.v[k2] = d4[at * ND + k2];
+      return d;
+    };
+    auto mean_vec = [&](const v4u& sv, const DVec& dv, int64_t at) {
       float acc[E];
 #pragma unroll
       for (int q = 0; q < E; ++q) acc[q] = 0.f;
-      add_vec(acc, sv, T{});
+      add_vec(acc, sv, TS{});
 #pragma unroll
       for (int q = 0; q < E; ++q) acc[q] = v > 0 ? acc[q] / fv : 0.f;
       if constexpr (AXPY) {
         float p[E];
 #pragma unroll
         for (int q = 0; q < E; ++q) p[q] = 0.f;
-        add_vec(p, dv, T{});
+#pragma unroll
+        for (int k2 = 0; k2 < ND; ++k2) add_vec(reinterpret_cast<float(&)[ED]>(p[k2 * ED]), dv.v[k2], TD{});
 #pragma unroll
         for (int q = 0; q < E; ++q) acc[q] = p[q] + alpha * acc[q];
       }
       if constexpr (SHADOW) {
-        if constexpr (E == 4) h2[at] = make_uint2(pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]));
+        // 4 bf16 per fp32 vector: 8 B per unit of the fp32 pass, 16 B of the mixed one
+        if constexpr (E == 4) {
+          reinterpret_cast<uint2*>(shadow + a)[at] =
+              make_uint2(pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3]));
+        } else {
+          reinterpret_cast<v4u*>(shadow + a)[at] = pack_vec(acc);
+        }
       }
-      return pack_vec(acc);
+#pragma unroll
+      for (int k2 = 0; k2 < ND; ++k2) d4[at * ND + k2] = pack_vec(reinterpret_cast<const float(&)[ED]>(acc[k2 * ED]));
     };
-    // kCmUnroll vectors per thread: every load of the group in flight before
+    // kCmUnroll units per thread: every load of the group in flight before
     // the first store (one vector at a time left the pass latency-bound)
     constexpr int U = kCmUnroll;
     const int64_t stride = int64_t(kBlock) * gridDim.y;
     int64_t i = int64_t(blockIdx.y) * kBlock + threadIdx.x;
     for (; i + (U - 1) * stride < nv; i += U * stride) {
-      v4u sv[U], dv[U];
+      v4u sv[U];
+      DVec dv[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) sv[u] = s4[i + u * stride];
+      if constexpr (AXPY) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) dv[u] = AXPY ? d4[i + u * stride] : sv[u];
+        for (int u = 0; u < U; ++u) dv[u] = load_d(i + u * stride);
+      }
 #pragma unroll
-      for (int u = 0; u < U; ++u) d4[i + u * stride] = mean_vec(sv[u], dv[u], i + u * stride);
+      for (int u = 0; u < U; ++u) mean_vec(sv[u], dv[u], i + u * stride);
     }
-    for (; i < nv; i += stride) d4[i] = mean_vec(s4[i], AXPY ? d4[i] : s4[i], i);
+    for (; i < nv; i += stride) {
+      DVec dv;
+      if constexpr (AXPY) dv = load_d(i);
+      mean_vec(s4[i], dv, i);
+    }
+  }
+}
+
+// ---- fp32 -> bf16 pack with error feedback (compressed gradient wire) ----------
+// q[i] = bf16_rne(e), e = g[i] + r[i]; r[i] = e - float(q[i]) in place (RES),
+// e = g[i] without a residual.  No multiply, so nothing contracts: g + r and
+// e - q are one IEEE fp32 operation each and float(q) + r == e exactly for
+// finite values.  Where e or q is not finite (a finite e may round to +-inf)
+// q is stored as is and r becomes 0, so one overflow does not stay in r.
+// head: elements below the first one that is 16-B aligned in all three
+// streams; block 0 does head and tail.  head < 0: the streams share no such
+// element, every element goes through the scalar path.  The body is units of
+// 8 elements: two 16-B loads of g (and of r) per 16-B store of q, 8 loads in
+// flight per thread before the first store (as count_mean's AXPY group).
+// NT: nontemporal loads and stores for streams past the Infinity Cache.
+
+template <bool RES>
+__device__ __forceinline__ unsigned short pack_one(float g, float& r) {
+  const float e = RES ? g + r : g;
+  const unsigned short q = from_f<unsigned short>(e);
+  if constexpr (RES) {
+    const float f = to_f(q);
+    // finite: exponent not all ones (f is inf or NaN whenever e is; f alone may be inf)
+    const bool fin = (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u;
+    r = fin ? e - f : 0.f;
+  }
+  return q;
+}
+
+template <bool RES, bool NT>
+__global__ __launch_bounds__(kBlock) void pack_bf16_kernel(unsigned short* __restrict__ q, const float* __restrict__ g,
+                                                           float* r, int64_t n, int64_t head) {
+  auto one = [&](int64_t i) {
+    float rr = RES ? r[i] : 0.f;
+    q[i] = pack_one<RES>(g[i], rr);
+    if constexpr (RES) r[i] = rr;
+  };
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  if (head < 0) {
+    for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) one(i);
+    return;
+  }
+  const int64_t nunit = (n - head) / 8;
+  if (blockIdx.x == 0) {
+    for (int64_t i = threadIdx.x; i < head; i += kBlock) one(i);
+    for (int64_t i = head + nunit * 8 + threadIdx.x; i < n; i += kBlock) one(i);
+  }
+  const v4u* g4 = reinterpret_cast<const v4u*>(g + head);
+  v4u* r4 = reinterpret_cast<v4u*>(r + head);
+  v4u* q4 = reinterpret_cast<v4u*>(q + head);
+  auto ld = [](const v4u* p) { return NT ? __builtin_nontemporal_load(p) : *p; };
+  auto st = [](const v4u& x, v4u* p) {
+    if constexpr (NT) __builtin_nontemporal_store(x, p);
+    else *p = x;
+  };
+  constexpr int U = RES ? 2 : 4;
+  for (int64_t base = int64_t(blockIdx.x) * kBlock + threadIdx.x; base < nunit; base += stride * U) {
+    v4u gv[U][2], rv[U][2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = base + u * stride;
+      if (i < nunit) {
+        gv[u][0] = ld(g4 + 2 * i);
+        gv[u][1] = ld(g4 + 2 * i + 1);
+        if constexpr (RES) {
+          rv[u][0] = ld(r4 + 2 * i);
+          rv[u][1] = ld(r4 + 2 * i + 1);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = base + u * stride;
+      if (i < nunit) {
+        unsigned short h[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          float rr = RES ? __uint_as_float(rv[u][k >> 2][k & 3]) : 0.f;
+          h[k] = pack_one<RES>(__uint_as_float(gv[u][k >> 2][k & 3]), rr);
+          if constexpr (RES) rv[u][k >> 2][k & 3] = __float_as_uint(rr);
+        }
+        if constexpr (RES) {
+          st(rv[u][0], r4 + 2 * i);
+          st(rv[u][1], r4 + 2 * i + 1);
+        }
+        st(v4u{uint32_t(h[0]) | uint32_t(h[1]) << 16, uint32_t(h[2]) | uint32_t(h[3]) << 16,
+               uint32_t(h[4]) | uint32_t(h[5]) << 16, uint32_t(h[6]) | uint32_t(h[7]) << 16},
+           q4 + i);
+      }
+    }
   }
 }
 
@@ -939,8 +1061,11 @@ void launch_xent_bwd(hipStream_t s, const void* x, const int64_t* y, int64_t B, 
 }
 
 void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t* counts, int64_t S, int64_t step,
-                       int32_t N, int64_t C, int32_t kmax, DType dt, bool axpy, float alpha, void* shadow) {
+                       int32_t N, int64_t C, int32_t kmax, DType dt, DType src_dt, bool axpy, float alpha,
+                       void* shadow) {
   if (S <= 0) return;
+  AKKA_CHECK(src_dt == dt || (dt == DType::F32 && src_dt == DType::BF16),
+             "count_mean: the source is the destination's dtype, or bf16 into fp32");
   AKKA_CHECK((reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0,
              "count_mean: buffers must be 16-B aligned");
   AKKA_CHECK(shadow == nullptr || (axpy && dt == DType::F32 && (reinterpret_cast<uintptr_t>(shadow) & 15) == 0),
@@ -957,20 +1082,61 @@ void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t*
   const int64_t useful = (per_region_vecs + kBlock - 1) / kBlock;
   if (split > useful) split = int(useful);
   if (split < 1) split = 1;
-#define AKKA_CM(T, AX, SH)                                                                                       \
-  hipLaunchKernelGGL((count_mean_kernel<T, AX, SH>), dim3(grid, split), dim3(kBlock), 0, s, static_cast<T*>(dst), \
-                     static_cast<const T*>(src), counts, S, step, N, C, kmax, alpha,                              \
+#define AKKA_CM(TD, TS, AX, SH)                                                                             \
+  hipLaunchKernelGGL((count_mean_kernel<TD, TS, AX, SH>), dim3(grid, split), dim3(kBlock), 0, s,             \
+                     static_cast<TD*>(dst), static_cast<const TS*>(src), counts, S, step, N, C, kmax, alpha, \
                      static_cast<unsigned short*>(shadow))
-  if (dt == DType::F32) {
-    if (shadow) AKKA_CM(float, true, true);
-    else if (axpy) AKKA_CM(float, true, false);
-    else AKKA_CM(float, false, false);
+  if (dt == DType::F32 && src_dt == DType::BF16) {
+    if (shadow) AKKA_CM(float, unsigned short, true, true);
+    else if (axpy) AKKA_CM(float, unsigned short, true, false);
+    else AKKA_CM(float, unsigned short, false, false);
+  } else if (dt == DType::F32) {
+    if (shadow) AKKA_CM(float, float, true, true);
+    else if (axpy) AKKA_CM(float, float, true, false);
+    else AKKA_CM(float, float, false, false);
   } else {
-    if (axpy) AKKA_CM(unsigned short, true, false);
-    else AKKA_CM(unsigned short, false, false);
+    if (axpy) AKKA_CM(unsigned short, unsigned short, true, false);
+    else AKKA_CM(unsigned short, unsigned short, false, false);
   }
 #undef AKKA_CM
   check_launch("count_mean");
+}
+
+void launch_pack_bf16(hipStream_t s, void* q, const float* g, float* r, int64_t n) {
+  if (n <= 0) return;
+  AKKA_CHECK((reinterpret_cast<uintptr_t>(q) & 1) == 0 && (reinterpret_cast<uintptr_t>(g) & 3) == 0 &&
+                 (reinterpret_cast<uintptr_t>(r) & 3) == 0,
+             "pack_bf16: buffers must be aligned to their element size");
+  // first element at which q, g and r are all 16-B aligned, if they share one
+  int64_t head = -1;
+  for (int64_t h = 0; h < 8 && head < 0; ++h) {
+    const bool ok = ((reinterpret_cast<uintptr_t>(q) + 2 * h) & 15) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(g) + 4 * h) & 15) == 0 &&
+                    (r == nullptr || ((reinterpret_cast<uintptr_t>(r) + 4 * h) & 15) == 0);
+    if (ok) head = h;
+  }
+  if (head > n) head = n;
+  // Cache policy and grid as the one-source reduce: everything fits the
+  // Infinity Cache -> plain accesses (the round reads q next), a grid over the
+  // whole stream; larger -> nontemporal loads and stores, 2 blocks/CU.
+  const int64_t bytes = n * (r ? 14 : 6);
+  const bool nt = bytes > (int64_t(256) << 20);
+  const int64_t per_block = int64_t(kBlock) * (head < 0 ? 1 : 8 * (r ? 2 : 4));
+  const int64_t cap = int64_t(kCUs) * (nt ? 2 : 16);
+  const int64_t want = (n + per_block - 1) / per_block;
+  const int grid = int(want < cap ? want : cap);
+#define AKKA_PK(RES, NT)                                                                     \
+  hipLaunchKernelGGL((pack_bf16_kernel<RES, NT>), dim3(grid), dim3(kBlock), 0, s,            \
+                     static_cast<unsigned short*>(q), g, r, n, head)
+  if (r) {
+    if (nt) AKKA_PK(true, true);
+    else AKKA_PK(true, false);
+  } else {
+    if (nt) AKKA_PK(false, true);
+    else AKKA_PK(false, false);
+  }
+#undef AKKA_PK
+  check_launch("pack_bf16");
 }
 
 }  // namespace akka

@@ -42,7 +42,16 @@ HOST_SOURCES = [
     "bindings/bind_onesided.cpp",
     "bindings/bind_probe.cpp",
 ]
-HIP_SOURCES = ["kernels/kernels.hip", "kernels/ipc.hip", "kernels/onesided.hip", "kernels/probe.hip"]
+HIP_SOURCES = [
+    "kernels/reduce.hip",
+    "kernels/counts.hip",
+    "kernels/pack_bf16.hip",
+    "kernels/colsum.hip",
+    "kernels/xent.hip",
+    "kernels/ipc.hip",
+    "kernels/onesided.hip",
+    "kernels/probe.hip",
+]
 
 
 def ext_path() -> str:

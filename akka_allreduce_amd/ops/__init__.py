@@ -1,4 +1,4 @@
-"""Device ops backed by the gfx950 kernels in ``csrc/kernels/kernels.hip``."""
+"""Device ops backed by the gfx950 kernels in ``csrc/kernels/`` (launchers: ``kernels.h``)."""
 from .colsum import colsum
 from .compress import pack_bf16
 from .reduce import chunk_reduce, count_expand

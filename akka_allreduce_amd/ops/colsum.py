@@ -3,7 +3,7 @@
 
 torch's generic reduction takes ~15 µs for a 256 x 8192 bf16 ``dY`` on
 MI355X (``profiles/r03/pass_h/cfg5_bf16_kernel_stats.csv``): a handful of
-workgroups walk all rows.  ``colsum_bf16_kernel`` (csrc/kernels/kernels.hip)
+workgroups walk all rows.  ``colsum_bf16_kernel`` (csrc/kernels/colsum.hip)
 splits the rows over enough workgroups to cover the chip and combines the
 fp32 partial rows deterministically in the last-arriving workgroup.
 

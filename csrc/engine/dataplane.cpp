@@ -21,7 +21,7 @@ DataPlane::DataPlane(Device* dev, const Geometry& g, int32_t me, int32_t ring_ro
   // 16-B vector loads need every pointer of a chunk reduce to share one
   // alignment: slot data starts at the same offset mod 16 B as my block does
   // in the caller's tensors (block_start * esize), and slot / row strides are
-  // multiples of 16 B (kernels.hip peels the common misaligned head).
+  // multiples of 16 B (reduce.hip peels the common misaligned head).
   const int64_t vec_el = int64_t(16 / esize());
   mis_el_ = g_.block_start(me_) % vec_el;
   slot_stride_ = (std::max<int64_t>(my_len_, 1) + mis_el_ + vec_el - 1) / vec_el * vec_el;

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "ipc_kernels.h"
+#include "launch_util.h"
 #include "xgmi_device.h"
 
 namespace akka {
@@ -90,7 +91,7 @@ __device__ inline void signal(uint32_t* f, uint32_t v) {  // lane 0, after relea
 // byte offset gather_off.
 // Vector body with the source count NS known at compile time: every thread
 // issues all NS x U 16-byte loads of an iteration before the first add (the
-// standalone reduce kernel's structure, kernels.hip), U = 16 / NS vectors per
+// standalone reduce kernel's structure, reduce.hip), U = 16 / NS vectors per
 // source, so ~16 loads are in flight per lane whatever N is.  Slot loads are
 // system-coherent buffer loads (sc0 sc1), or -- `plain_slots`, measured
 // against them -- plain loads behind the workgroup's system-scope acquire.
@@ -130,9 +131,9 @@ __device__ void reduce_vec_n(const IpcArgs& a, const char* mine, const char* slo
 #pragma unroll
       for (int e = 0; e < PV; ++e) acc[e] = 0.f;
 #pragma unroll
-      for (int s = 0; s < NS; ++s) Elt<T>::add(acc, v[s][u]);
+      for (int s = 0; s < NS; ++s) add<T>(acc, v[s][u]);
       if (i < nv) {
-        const uint4 w = Elt<T>::pack(acc);
+        const uint4 w = pack<T>(acc);
         // my output: read by this rank only, after the round -- streamed past
         // the caches so it does not evict the slots still to be read
         store_nt16(reinterpret_cast<uint4*>(o) + i, w);
@@ -194,13 +195,13 @@ __device__ bool reduce_span(const IpcArgs& a, const char* mine, const char* slot
           for (int u = 0; u < kUnroll; ++u) v[u] = load_sys16(r, (i0 + int64_t(u) * int(blockDim.x)) * 16);  // 0 past the end
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) Elt<T>::add(acc[u], v[u]);
+        for (int u = 0; u < kUnroll; ++u) add<T>(acc[u], v[u]);
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int64_t i = i0 + int64_t(u) * int(blockDim.x);
         if (i < nv) {
-          const uint4 w = Elt<T>::pack(acc[u]);
+          const uint4 w = pack<T>(acc[u]);
           reinterpret_cast<uint4*>(o)[i] = w;
           if (bc) {
             for (int p = 0; p < N; ++p)
@@ -216,7 +217,7 @@ __device__ bool reduce_span(const IpcArgs& a, const char* mine, const char* slot
       float acc = 0.f;
       for (int s = 0; s < N; ++s)
         acc += s == me ? Elt<T>::load1(mine + i * ES)
-                       : Elt<T>::load1_sys(sys_rsrc(slots + int64_t(s) * slot_bytes, n * ES), i * ES);
+                       : load1_sys<T>(sys_rsrc(slots + int64_t(s) * slot_bytes, n * ES), i * ES);
       Elt<T>::store1(o + i * ES, acc);
       if (bc) {
         for (int p = 0; p < N; ++p)
@@ -412,23 +413,6 @@ void launch_reduce(hipStream_t s, const IpcArgs& a, unsigned grid, unsigned nt) 
     hipLaunchKernelGGL((ipc_reduce_kernel<T, NS, kMaxThreads>), dim3(grid), dim3(nt), 0, s, a);
 }
 
-// Calls f(std::integral_constant<int, NS>) with NS = N for the node's rank
-// counts (2..8, 16) and NS = 0 (runtime N) otherwise.
-template <typename F>
-void with_ns(int32_t N, F&& f) {
-  switch (N) {
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 5: return f(std::integral_constant<int, 5>{});
-    case 6: return f(std::integral_constant<int, 6>{});
-    case 7: return f(std::integral_constant<int, 7>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    default: return f(std::integral_constant<int, 0>{});
-  }
-}
-
 template <typename T, int NS>
 void launch_round(hipStream_t s, const IpcArgs& a) {
   constexpr int ES = sizeof(T);
@@ -554,7 +538,7 @@ void launch_ipc_round(hipStream_t s, const IpcArgs& a, DType dt) {
   if (a.N < 2) return;
   with_ns(a.N, [&](auto ns) {
     if (dt == DType::F32) launch_round<float, decltype(ns)::value>(s, a);
-    else launch_round<uint16_t, decltype(ns)::value>(s, a);
+    else launch_round<bf16_t, decltype(ns)::value>(s, a);
   });
 }
 
@@ -629,7 +613,7 @@ double ipc_reduce_role_bench(int32_t N, int64_t block, int64_t portion_bytes, DT
   auto launch = [&]() {
     with_ns(N, [&](auto ns) {
       if (dt == DType::F32) launch_reduce<float, decltype(ns)::value>(nullptr, a, grid, unsigned(nt));
-      else launch_reduce<uint16_t, decltype(ns)::value>(nullptr, a, grid, unsigned(nt));
+      else launch_reduce<bf16_t, decltype(ns)::value>(nullptr, a, grid, unsigned(nt));
     });
   };
   for (int i = 0; i < 3; ++i) launch();

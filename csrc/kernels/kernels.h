@@ -1,4 +1,5 @@
-// Launchers for the gfx950 kernels (kernels.hip).
+// Launchers for the gfx950 kernels (reduce.hip, counts.hip, pack_bf16.hip,
+// colsum.hip, xent.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -28,6 +28,7 @@
 #include <string>
 #include <type_traits>
 
+#include "launch_util.h"
 #include "onesided_kernels.h"
 #include "xgmi_device.h"
 
@@ -374,9 +375,9 @@ __device__ void masked_sum_n(const Args& a, const char* mine, const char* sd, ch
       for (int e = 0; e < PV; ++e) acc[e] = 0.f;
 #pragma unroll
       for (int s = 0; s < NS; ++s)
-        if ((mask >> s) & 1u) Elt<T>::add(acc, v[s][u]);
+        if ((mask >> s) & 1u) add<T>(acc, v[s][u]);
       if (i < nv) {
-        const uint4 w = Elt<T>::pack(acc);
+        const uint4 w = pack<T>(acc);
         if (a.own_wt) store_sys16(sys_rsrc(o, nv * 16), i * 16, w);
         else store_nt16(reinterpret_cast<uint4*>(o) + i, w);
         if (a.fenced) {  // plain stores, released before the tags (reduce_piece)
@@ -435,13 +436,13 @@ __device__ bool masked_sum(const Args& a, char* out, int32_t row, uint32_t mask,
           for (int u = 0; u < kUnroll; ++u) v[u] = load_sys16(rs, (i0 + int64_t(u) * int(blockDim.x)) * 16);
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) Elt<T>::add(acc[u], v[u]);
+        for (int u = 0; u < kUnroll; ++u) add<T>(acc[u], v[u]);
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         const int64_t i = i0 + int64_t(u) * int(blockDim.x);
         if (i < nv) {
-          const uint4 w = Elt<T>::pack(acc[u]);
+          const uint4 w = pack<T>(acc[u]);
           reinterpret_cast<uint4*>(o)[i] = w;
           for (int32_t q = 0; q < N; ++q)
             if ((okq >> q) & 1u) reinterpret_cast<uint4*>(a.tab->gd[row][q] + goff)[i] = w;
@@ -454,7 +455,7 @@ __device__ bool masked_sum(const Args& a, char* out, int32_t row, uint32_t mask,
       for (int32_t s = 0; s < N; ++s) {
         if (!((mask >> s) & 1u)) continue;
         acc += s == me ? Elt<T>::load1(mine + i * ES)
-                       : Elt<T>::load1_sys(sys_rsrc(sd + (int64_t(s) * a.slot + off) * ES, n * ES), i * ES);
+                       : load1_sys<T>(sys_rsrc(sd + (int64_t(s) * a.slot + off) * ES, n * ES), i * ES);
       }
       Elt<T>::store1(o + i * ES, acc);
       for (int32_t q = 0; q < N; ++q)
@@ -875,21 +876,6 @@ __global__ __launch_bounds__(LB) void os_reduce_bench_kernel(Args a, uint32_t r)
     reduce_piece<T, NS>(a, a.out, r, w / (P * ns), (w / ns) % P, w % ns, false);
 }
 
-template <typename F>
-void with_ns(int32_t N, F&& f) {
-  switch (N) {
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 5: return f(std::integral_constant<int, 5>{});
-    case 6: return f(std::integral_constant<int, 6>{});
-    case 7: return f(std::integral_constant<int, 7>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    default: return f(std::integral_constant<int, 0>{});
-  }
-}
-
 template <typename T>
 void launch_call(hipStream_t s, const Args& a) {
   const unsigned nt = a.threads <= 256 ? 256u : 1024u;
@@ -909,7 +895,7 @@ void launch_onesided_retire(hipStream_t s, const Args& a) {
 
 void launch_onesided_call(hipStream_t s, const Args& a, int32_t dtype) {
   if (dtype == 0) launch_call<float>(s, a);
-  else launch_call<uint16_t>(s, a);
+  else launch_call<bf16_t>(s, a);
 }
 
 double onesided_reduce_role_bench(int32_t N, int64_t block, int64_t chunk, int64_t part, int32_t nsub, int32_t dtype,
@@ -990,7 +976,7 @@ double onesided_reduce_role_bench(int32_t N, int64_t block, int64_t chunk, int64
       });
     };
     if (dtype == 0) go(float{});
-    else go(uint16_t{});
+    else go(bf16_t{});
   };
   hipEvent_t e0, e1;
   ok(hipEventCreate(&e0), "event");

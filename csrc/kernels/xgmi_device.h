@@ -19,6 +19,8 @@
 
 #include <cstdint>
 
+#include "elem.h"
+
 namespace akka {
 namespace xgmi {
 
@@ -57,17 +59,15 @@ __device__ inline bool acquire_all(bool ok_lane0) {
   return ok != 0;
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // Streaming (nontemporal) 16-byte store of local memory nobody reads before
 // the kernel ends: it does not evict the lines still to be read.
 __device__ inline void store_nt16(uint4* p, const uint4& v) {
-  u32x4 w;
+  v4u w;
   w[0] = v.x;
   w[1] = v.y;
   w[2] = v.z;
   w[3] = v.w;
-  __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
+  __builtin_nontemporal_store(w, reinterpret_cast<v4u*>(p));
 }
 
 // dst <- src with plain loads and stores (src is this rank's own memory).
@@ -110,6 +110,12 @@ __device__ inline uint4 load_sys16(__amdgpu_buffer_rsrc_t r, int64_t off) {
   const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, int(off), 0, kSysAux);
   return make_uint4(v[0], v[1], v[2], v[3]);
 }
+// One element as fp32 (the unaligned bodies).
+template <typename T>
+__device__ inline float load1_sys(__amdgpu_buffer_rsrc_t r, int64_t off) {
+  if constexpr (sizeof(T) == 4) return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, int(off), 0, kSysAux));
+  else return Elt<T>::to_f(T(__builtin_amdgcn_raw_buffer_load_b16(r, int(off), 0, kSysAux)));
+}
 
 // dst (local, streamed past the caches: the round's output, read after the
 // round) <- src (window memory written by a peer).
@@ -146,7 +152,7 @@ __device__ inline void copy_in(char* __restrict__ dst, const char* __restrict__ 
 // (docs/DESIGN.md section 4f rule 3: write-through stores + drained flag; sc
 // loads in place of the acquire), at system scope.
 __device__ inline void store_sys16(__amdgpu_buffer_rsrc_t r, int64_t off, const uint4& v) {
-  u32x4 w;
+  v4u w;
   w[0] = v.x;
   w[1] = v.y;
   w[2] = v.z;
@@ -190,58 +196,19 @@ __device__ inline void zero_bytes(char* __restrict__ dst, int64_t bytes) {
   }
 }
 
-__device__ inline float bf16_to_f32(uint16_t h) { return __uint_as_float(uint32_t(h) << 16); }
-__device__ inline uint16_t f32_to_bf16(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) return uint16_t((u >> 16) | 0x40);  // quiet NaN
-  return uint16_t((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-// Element codecs: a 16-B vector <-> fp32 accumulators (bf16 via RNE).
+// The codec (elem.h) on HIP's uint4, the type these kernels hold their vectors
+// in: with the native vector in its place the compiler keeps whole 16-B
+// values where it splits a uint4 into halves, and the fp32 round kernels come
+// out with other scalar code (slower at small blocks, profiles/r08/kernel_split/).
 template <typename T>
-struct Elt;
-template <>
-struct Elt<float> {
-  static constexpr int kPerVec = 4;
-  __device__ static void add(float* acc, const uint4& v) {
-    acc[0] += __uint_as_float(v.x);
-    acc[1] += __uint_as_float(v.y);
-    acc[2] += __uint_as_float(v.z);
-    acc[3] += __uint_as_float(v.w);
-  }
-  __device__ static uint4 pack(const float* acc) {
-    return make_uint4(__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]),
-                      __float_as_uint(acc[3]));
-  }
-  __device__ static float load1(const char* p) { return *reinterpret_cast<const float*>(p); }
-  __device__ static float load1_sys(__amdgpu_buffer_rsrc_t r, int64_t off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, int(off), 0, kSysAux));
-  }
-  __device__ static void store1(char* p, float v) { *reinterpret_cast<float*>(p) = v; }
-};
-template <>
-struct Elt<uint16_t> {
-  static constexpr int kPerVec = 8;
-  __device__ static void add(float* acc, const uint4& v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[2 * i] += __uint_as_float(w[i] << 16);
-      acc[2 * i + 1] += __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ static uint4 pack(const float* acc) {
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = uint32_t(f32_to_bf16(acc[2 * i])) | (uint32_t(f32_to_bf16(acc[2 * i + 1])) << 16);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-  }
-  __device__ static float load1(const char* p) { return bf16_to_f32(*reinterpret_cast<const uint16_t*>(p)); }
-  __device__ static float load1_sys(__amdgpu_buffer_rsrc_t r, int64_t off) {
-    return bf16_to_f32(uint16_t(__builtin_amdgcn_raw_buffer_load_b16(r, int(off), 0, kSysAux)));
-  }
-  __device__ static void store1(char* p, float v) { *reinterpret_cast<uint16_t*>(p) = f32_to_bf16(v); }
-};
+__device__ inline void add(float (&acc)[Elt<T>::kPerVec], const uint4& v) {
+  Elt<T>::add(acc, v4u{v.x, v.y, v.z, v.w});
+}
+template <typename T>
+__device__ inline uint4 pack(const float (&acc)[Elt<T>::kPerVec]) {
+  const v4u w = Elt<T>::pack(acc);
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
 
 }  // namespace xgmi
 }  // namespace akka

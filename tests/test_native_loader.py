@@ -27,7 +27,7 @@ def tree(tmp_path):
 def test_hash_tracks_contents_not_timestamps(tree):
     root, ext = tree
     assert _build.stale_reason(ext, str(root)) is None
-    src = root / "csrc" / "kernels" / "kernels.hip"
+    src = root / "csrc" / "kernels" / "reduce.hip"
     t = os.path.getmtime(src)
     os.utime(src, (t + 3600, t + 3600))  # a newer timestamp alone changes nothing
     assert _build.stale_reason(ext, str(root)) is None

@@ -45,6 +45,7 @@ HOST_SOURCES = [
 HIP_SOURCES = [
     "kernels/reduce.hip",
     "kernels/counts.hip",
+    "kernels/optim.hip",
     "kernels/pack_bf16.hip",
     "kernels/colsum.hip",
     "kernels/xent.hip",

@@ -65,6 +65,20 @@ class Geometry:
         return per_chunk.reshape(-1)[blk * self.kmax + k].to(torch.int32)
 
 
+def sqnorm_workspace(device) -> torch.Tensor:
+    """Workspace of ``AllReduceOutput.sqnorm`` (the global-norm clip of
+    ``optim_step_``): the result, the kernel's ticket and one partial per
+    workgroup.  Zeroed once here; every pass leaves the ticket zero again, so
+    one workspace serves every step, and every replay of a captured one."""
+    device = torch.device(device)
+    n = 0
+    if device.type == "cuda":
+        from ._native_loader import load
+
+        n = load().count_sqnorm_partials()
+    return torch.zeros(2 + n, dtype=torch.float32, device=device)
+
+
 @dataclass
 class AllReduceInputRequest:
     iteration: int
@@ -176,6 +190,134 @@ class AllReduceOutput:
         if shadow is not None:
             shadow.copy_(y.view_as(shadow))
         return y
+
+    def optim_step_(self, kind: str, p: torch.Tensor, m: torch.Tensor, v: Optional[torch.Tensor], t: torch.Tensor,
+                    lr: float, *, weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
+                    betas: tuple = (0.9, 0.999), eps: float = 1e-8, shadow: Optional[torch.Tensor] = None,
+                    max_norm: Optional[float] = None, norm_ws: Optional[torch.Tensor] = None,
+                    nt: bool = False) -> torch.Tensor:
+        """One optimizer step of the flat fp32 parameters ``p`` from this
+        round, in one fused pass on the GPU: per element ``g = sum / count``,
+        then ``kind="sgd"`` (``torch.optim.SGD``: weight decay into ``g``,
+        ``m = momentum * m + g``, Nesterov or not, dampening 0) or
+        ``kind="adamw"`` (``torch.optim.AdamW``: decoupled decay, ``m`` / ``v``
+        with the bias corrections of step ``t``).  ``m`` and ``v`` are the
+        flat fp32 state (``v`` only for AdamW); ``t`` is the step, one int32 on
+        ``p``'s device, already advanced for this step by the caller.  A bf16
+        sum (a compressed wire) is read wide into fp32.  ``shadow`` (bf16)
+        receives the updated parameters from the same pass.
+
+        ``max_norm`` clips by the global norm as ``clip_grad_norm_`` does:
+        ``g`` is scaled by ``min(1, max_norm / (norm + 1e-6))``, the norm taken
+        over the mean gradient of this round (one extra pass over the sum into
+        ``norm_ws``, see ``sqnorm``) and read on the device, no host sync.
+
+        A chunk whose count is 0 is MISSING, not zero: its ``p``, ``m``, ``v``
+        and ``shadow`` stay exactly as they are (stale momentum must not move a
+        parameter whose gradient a threshold round dropped); the bias
+        corrections still use the global ``t``.
+
+        CUDA tensors always go to the native kernel, under the conditions of
+        ``axpy_mean_``'s fused pass (anything else raises); CPU tensors run the
+        same formulas as torch operations.  ``nt`` streams with nontemporal
+        accesses instead of plain ones (slower where measured: kept for
+        ``bench/fused_opt.py``).  Returns ``p``."""
+        self.wait()
+        if kind not in ("sgd", "adamw"):
+            raise ValueError(f"optim_step_: kind={kind!r} (sgd or adamw)")
+        adam = kind == "adamw"
+        d = self.data
+        if d.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"optim_step_: a float32 or bfloat16 sum, not {d.dtype}")
+        state =[("m", m)] + ([("v", v)] if adam else [])
+        for name, s in [("p", p)] + state:
+            if s is None or s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != d.numel() \
+                    or s.device != d.device:
+                raise ValueError(f"optim_step_: {name} must be contiguous float32 of the round's size and device")
+        if shadow is not None and (shadow.dtype != torch.bfloat16 or not shadow.is_contiguous()
+                                   or shadow.numel() != p.numel() or shadow.device != p.device):
+            raise ValueError("optim_step_: shadow must be contiguous bfloat16 of p's size and device")
+        if t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device:
+            raise ValueError("optim_step_: t is one int32 on p's device")
+        if max_norm is not None and norm_ws is None:
+            raise ValueError("optim_step_: max_norm needs a norm workspace (sqnorm_workspace)")
+        if d.is_cuda:
+            wide = self._is_wide(p.dtype)
+            if not (self._fused_ok(p, wide) and all(s.data_ptr() % 16 == 0 for _, s in state)
+                    and (shadow is None or shadow.data_ptr() % 16 == 0)):
+                raise ValueError("optim_step_: the fused pass needs a float32 or bfloat16 sum with its per-chunk "
+                                 "counts (not expanded) and 16-B aligned buffers")
+            from ._native_loader import load
+
+            sq = self.sqnorm(norm_ws) if max_norm is not None else None
+            g = self.geometry
+            pc = self.counts_per_chunk.contiguous()
+            load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
+                               shadow.data_ptr() if shadow is not None else 0, d.data_ptr(),
+                               "bfloat16" if d.dtype == torch.bfloat16 else "float32", pc.data_ptr(), g.dataSize,
+                               g.step, g.workerNum, g.maxChunkSize, g.kmax, t.data_ptr(),
+                               sq.data_ptr() if sq is not None else 0, float(lr), float(weight_decay),
+                               float(momentum), bool(nesterov), float(betas[0]), float(betas[1]), float(eps),
+                               float(max_norm) if max_norm is not None else 0.0,
+                               torch.cuda.current_stream(d.device).cuda_stream, bool(nt))
+            return p
+        # the same formulas as torch operations (count-0 elements keep everything)
+        keep = (self.count <= 0).view_as(p)
+        g = self.mean(dtype=torch.float32) if d.dtype != torch.float32 else self.mean()
+        g = g.view_as(p)
+        if max_norm is not None:
+            sq = self.sqnorm(norm_ws)
+            g = g * torch.clamp(max_norm / (sq.sqrt() + 1e-6), max=1.0)
+        if adam:
+            b1, b2 = betas
+            tf = t.to(torch.float32)
+            pn = p * (1 - lr * weight_decay)
+            mn = torch.lerp(m, g, 1 - b1)
+            vn = (v * b2).addcmul_(g, g, value=1 - b2)
+            # p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps), bc_k = 1 - b_k^t, with the step size folded
+            # into the denominator as AdamW(capturable=True) and the kernel spell it
+            nss = -(lr / (1 - b1 ** tf))
+            pn = pn.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(eps / nss))
+            v.copy_(torch.where(keep, v, vn))
+        else:
+            g = g.add(p, alpha=weight_decay)
+            mn = (m * momentum).add_(g)
+            pn = p.add(g.add(mn, alpha=momentum) if nesterov else mn, alpha=-lr)
+        m.copy_(torch.where(keep, m, mn))
+        p.copy_(torch.where(keep, p, pn))
+        if shadow is not None:
+            shadow.copy_(torch.where(keep.view_as(shadow), shadow, p.view_as(shadow).to(shadow.dtype)))
+        return p
+
+    def sqnorm(self, ws: torch.Tensor) -> torch.Tensor:
+        """Squared global norm of this round's mean gradient: the sum over the
+        elements whose count is > 0 of ``(sum / count) ** 2``, in fp32, as a
+        one-element view of the workspace ``ws`` (``sqnorm_workspace``).  On
+        the GPU one pass over the sum (fp32 or bf16), deterministic for a
+        given shape; no host sync."""
+        self.wait()
+        d = self.data
+        if ws.dtype != torch.float32 or ws.device != d.device or not ws.is_contiguous():
+            raise ValueError("sqnorm: the workspace is float32 on the round's device (sqnorm_workspace)")
+        if d.is_cuda:
+            from ._native_loader import load
+
+            nat = load()
+            if not (d.dtype in (torch.float32, torch.bfloat16) and self.counts_per_chunk is not None
+                    and self.geometry is not None and d.is_contiguous() and d.data_ptr() % 16 == 0
+                    and ws.numel() >= 2 + nat.count_sqnorm_partials()):
+                raise ValueError("sqnorm: needs a 16-B aligned float32 or bfloat16 sum with its per-chunk counts "
+                                 "and a workspace from sqnorm_workspace")
+            g = self.geometry
+            pc = self.counts_per_chunk.contiguous()
+            # [0]: the result, [1]: the ticket (zero bits), [2:]: one partial per workgroup
+            nat.count_sqnorm(ws.data_ptr(), d.data_ptr(), "bfloat16" if d.dtype == torch.bfloat16 else "float32",
+                             pc.data_ptr(), g.dataSize, g.step, g.workerNum, g.maxChunkSize, g.kmax,
+                             ws.data_ptr() + 8, ws.data_ptr() + 4, torch.cuda.current_stream(d.device).cuda_stream)
+            return ws[:1]
+        g = self.mean(dtype=torch.float32) if d.dtype != torch.float32 else self.mean()
+        ws[0] = (g * g).sum()
+        return ws[:1]
 
     def mean(self, out: Optional[torch.Tensor] = None, *, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """Element-wise average over the contributors that made it (0 where none).

@@ -136,7 +136,8 @@ class MLP(nn.Module):
 def dp_sgd_step(model: nn.Module, x: torch.Tensor, y: torch.Tensor, lr: float,
                 allreduce: Optional[AllreduceFn], bucket: Optional[GradientBucket] = None,
                 sync_loss: bool = True, compute_dtype: Optional[torch.dtype] = None,
-                direct_grads: bool = True, shadow_weights: bool = True, fused_loss: bool = True):
+                direct_grads: bool = True, shadow_weights: bool = True, fused_loss: bool = True,
+                optimizer=None):
     """forward + backward + gradient allreduce (mean over contributors) + SGD
     update.  With a bucket built with ``flatten_params=True`` the averaging and
     the update are one fused pass.  ``sync_loss=False`` returns the loss as a
@@ -145,14 +146,23 @@ def dp_sgd_step(model: nn.Module, x: torch.Tensor, y: torch.Tensor, lr: float,
     gradients, the allreduce and the update stay fp32; with
     ``shadow_weights`` the fused update also stores the bf16 weight copy the
     next step's GEMMs read (``GradientBucket.use_shadow``), so no step casts
-    the fp32 weights again."""
+    the fp32 weights again.  ``optimizer`` (``parallel.FusedSGD`` /
+    ``FusedAdamW`` on this bucket) replaces the plain SGD update with its own
+    fused pass; ``lr`` is then its learning rate for this step."""
+    if optimizer is not None:
+        if bucket is not None and optimizer.bucket is not bucket:
+            raise ValueError("dp_sgd_step: the optimizer was built on another bucket")
+        bucket = optimizer.bucket
     if bucket is None:
         bucket = getattr(model, "_akka_bucket", None)
         if bucket is None:
             bucket = GradientBucket(list(model.parameters()))
             model._akka_bucket = bucket  # type: ignore[attr-defined]
     loss = _forward_backward(model, x, y, bucket, compute_dtype, direct_grads, shadow_weights, fused_loss)
-    bucket.sgd_from(allreduce, lr)
+    if optimizer is None:
+        bucket.sgd_from(allreduce, lr)
+    else:
+        optimizer.step_from(allreduce, lr)
     return float(loss.detach()) if sync_loss else loss.detach()
 
 
@@ -202,7 +212,10 @@ class GraphedDPStep:
     eagerly -- an allreduce with a per-round host protocol (the engine's
     lanes) stays outside the graph.  ``allreduce=`` a capturable one (the
     one-sided lane, ``OneSidedAllreduce``) and ``lr=`` capture the WHOLE
-    step: forward, backward, allreduce and update in one replay.  The ~30 launches of
+    step: forward, backward, allreduce and update in one replay.  ``optimizer=``
+    (``parallel.FusedSGD`` / ``FusedAdamW`` on this bucket) puts its fused pass
+    where the plain SGD update is, captured or not; its step counter lives on
+    the device, so a captured update advances it on every replay.  The ~30 launches of
     the forward/backward cost one replay instead of ~10 µs of host time each
     (the step is otherwise host-bound at this size).
 
@@ -214,12 +227,14 @@ class GraphedDPStep:
 
     def __init__(self, model: "MLP", bucket: GradientBucket, x: torch.Tensor, y: torch.Tensor,
                  compute_dtype: Optional[torch.dtype] = None, shadow_weights: bool = True, warmup: int = 3,
-                 allreduce: Optional[AllreduceFn] = None, lr: Optional[float] = None):
+                 allreduce: Optional[AllreduceFn] = None, lr: Optional[float] = None, optimizer=None):
         if not (x.is_cuda and isinstance(model, MLP)):
             raise ValueError("GraphedDPStep: an MLP on a GPU")
+        if optimizer is not None and optimizer.bucket is not bucket:
+            raise ValueError("GraphedDPStep: the optimizer was built on another bucket")
         if bucket.pflat is None or not bucket.bound() or not bucket.params_bound():
             raise ValueError("GraphedDPStep: needs GradientBucket(flatten_params=True) bound to the model")
-        self.model, self.bucket = model, bucket
+        self.model, self.bucket, self.optimizer = model, bucket, optimizer
         self.compute_dtype = compute_dtype
         self.lowp = compute_dtype if (shadow_weights and compute_dtype is not None
                                       and compute_dtype != torch.float32) else None
@@ -254,7 +269,9 @@ class GraphedDPStep:
         def fb():
             loss = _forward_backward(model, self.sx, self.sy, bucket, compute_dtype, True, shadow_weights, True,
                                      grad_seed=self._seed)
-            if self.allreduce is not None:
+            if self.allreduce is not None and optimizer is not None:
+                optimizer.step_from(self.allreduce, float(lr), out_buf=self._out)
+            elif self.allreduce is not None:
                 bucket.sgd_from(self.allreduce, float(lr), out_buf=self._out)
             return loss
 
@@ -268,6 +285,9 @@ class GraphedDPStep:
         snap = bucket.pflat.clone() if self.allreduce is not None else None
         # ... and so is a compressed bucket's error-feedback residual
         rsnap = bucket.residual.clone() if (self.allreduce is not None and bucket.residual is not None) else None
+        # ... and the optimizer's state and step counter
+        osnap = [s.clone() for s in optimizer.state_tensors()] \
+            if (self.allreduce is not None and optimizer is not None) else None
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 fb()
@@ -286,6 +306,9 @@ class GraphedDPStep:
             bucket._shadow_versions = [p._version for p in bucket.params]
         if rsnap is not None:
             bucket.residual.copy_(rsnap)
+        if osnap is not None:
+            for s, keep in zip(optimizer.state_tensors(), osnap):
+                s.copy_(keep)
         self._ptrs = self._pointers()  # the shadow exists now
 
     def static_inputs(self):
@@ -297,14 +320,15 @@ class GraphedDPStep:
         b = self.bucket
         return (b.flat.data_ptr(), b.pflat.data_ptr(), b.sflat.data_ptr() if b.sflat is not None else 0,
                 [p.data_ptr() for p in b.params], [p.grad.data_ptr() if p.grad is not None else 0 for p in b.params],
-                b.wire.data_ptr() if b.wire is not None else 0, b.residual.data_ptr() if b.residual is not None else 0)
+                b.wire.data_ptr() if b.wire is not None else 0, b.residual.data_ptr() if b.residual is not None else 0,
+                self.optimizer.state_pointers() if self.optimizer is not None else ())
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, lr: float, allreduce: Optional[AllreduceFn],
                  sync_loss: bool = False):
         b = self.bucket
         if self._pointers() != self._ptrs:
-            raise RuntimeError("GraphedDPStep: a parameter, gradient, shadow, wire or residual buffer moved "
-                               "since the capture")
+            raise RuntimeError("GraphedDPStep: a parameter, gradient, shadow, wire, residual or optimizer state "
+                               "buffer moved since the capture")
         if b.use_shadow(self.lowp) != (self.lowp is not None and b.sflat is not None):
             raise RuntimeError("GraphedDPStep: the bf16 shadow is no longer usable")
         if x.data_ptr() != self.sx.data_ptr():
@@ -323,7 +347,10 @@ class GraphedDPStep:
                 b._shadow_versions = [p._version for p in b.params]
         else:
             self.graph.replay()
-            b.sgd_from(allreduce, lr)
+            if self.optimizer is None:
+                b.sgd_from(allreduce, lr)
+            else:
+                self.optimizer.step_from(allreduce, lr)
         return float(self.loss) if sync_loss else self.loss
 
 

@@ -1,4 +1,5 @@
 """Distributed runtimes: SPMD/torchrun collective, master-driven cluster, simulators."""
 from .collective import ThresholdAllreduce, env_rank_world, share_unique_id
+from .optim import FusedAdamW, FusedSGD
 
-__all__ = ["ThresholdAllreduce", "env_rank_world", "share_unique_id"]
+__all__ = ["ThresholdAllreduce", "env_rank_world", "share_unique_id", "FusedSGD", "FusedAdamW"]

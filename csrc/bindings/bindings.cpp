@@ -1080,6 +1080,43 @@ PYBIND11_MODULE(_native, m) {
   }, py::arg("dst"), py::arg("src"), py::arg("counts"), py::arg("S"), py::arg("step"), py::arg("N"), py::arg("C"),
      py::arg("kmax"), py::arg("dtype"), py::arg("stream"), py::arg("axpy") = false, py::arg("alpha") = 0.f,
      py::arg("shadow") = 0, py::arg("src_dtype") = "");
+  m.def("count_optim", [](std::string kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow, uintptr_t src,
+                          std::string src_dtype, uintptr_t counts, int64_t S, int64_t step, int32_t N, int64_t C,
+                          int32_t kmax, uintptr_t t, uintptr_t sq, double lr, double weight_decay, double momentum,
+                          bool nesterov, double beta1, double beta2, double eps, double max_norm, uintptr_t stream,
+                          bool nt) {
+    AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim: kind is 'sgd' or 'adamw'");
+    AKKA_CHECK(src_dtype == "float32" || src_dtype == "bfloat16", "count_optim: the sum is float32 or bfloat16");
+    OptimSpec o;
+    o.kind = kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD;
+    o.lr = lr;
+    o.weight_decay = weight_decay;
+    o.momentum = momentum;
+    o.nesterov = nesterov;
+    o.beta1 = beta1;
+    o.beta2 = beta2;
+    o.eps = eps;
+    o.max_norm = max_norm;
+    launch_count_optim(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<float*>(mom),
+                       reinterpret_cast<float*>(v), reinterpret_cast<void*>(shadow),
+                       reinterpret_cast<const void*>(src), src_dtype == "bfloat16" ? DType::BF16 : DType::F32,
+                       reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax, o,
+                       reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), nt);
+  }, py::arg("kind"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("src"),
+     py::arg("src_dtype"), py::arg("counts"), py::arg("S"), py::arg("step"), py::arg("N"), py::arg("C"),
+     py::arg("kmax"), py::arg("t"), py::arg("sq"), py::arg("lr"), py::arg("weight_decay") = 0.0,
+     py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+     py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0, py::arg("stream") = 0, py::arg("nt") = false);
+  m.def("count_sqnorm", [](uintptr_t sq, uintptr_t src, std::string src_dtype, uintptr_t counts, int64_t S,
+                           int64_t step, int32_t N, int64_t C, int32_t kmax, uintptr_t part, uintptr_t ticket,
+                           uintptr_t stream) {
+    AKKA_CHECK(src_dtype == "float32" || src_dtype == "bfloat16", "count_sqnorm: the sum is float32 or bfloat16");
+    launch_count_sqnorm(as_stream(stream), reinterpret_cast<float*>(sq), reinterpret_cast<const void*>(src),
+                        src_dtype == "bfloat16" ? DType::BF16 : DType::F32, reinterpret_cast<const int32_t*>(counts),
+                        S, step, N, C, kmax, reinterpret_cast<float*>(part), reinterpret_cast<uint32_t*>(ticket));
+  }, py::arg("sq"), py::arg("src"), py::arg("src_dtype"), py::arg("counts"), py::arg("S"), py::arg("step"),
+     py::arg("N"), py::arg("C"), py::arg("kmax"), py::arg("part"), py::arg("ticket"), py::arg("stream") = 0);
+  m.def("count_sqnorm_partials", &count_sqnorm_partials);
   m.def("pack_bf16", [](uintptr_t dst, uintptr_t src, uintptr_t residual, int64_t n, uintptr_t stream) {
     AKKA_CHECK(n >= 0 && (n == 0 || (dst != 0 && src != 0)), "pack_bf16: null buffer");
     launch_pack_bf16(as_stream(stream), reinterpret_cast<void*>(dst), reinterpret_cast<const float*>(src),

@@ -185,22 +185,6 @@ __global__ void fill_counts_kernel(const uint32_t* flag, int32_t* counts, int64_
     counts[i] = v;
 }
 
-// Workgroups of a region walk: one per region up to max_grid, and `split`
-// workgroups sharing a region (gridDim.y) while there are few regions and a
-// region has the vectors to keep them busy.
-struct RegionGrid {
-  int grid, split;
-};
-RegionGrid region_grid(int64_t regions, int64_t S, int64_t max_grid) {
-  const int grid = int(regions < max_grid ? regions : max_grid);
-  int split = int(max_grid / grid);
-  const int64_t per_region_vecs = (S / regions) / 4 + 1;
-  const int64_t useful = (per_region_vecs + kBlock - 1) / kBlock;
-  if (split > useful) split = int(useful);
-  if (split < 1) split = 1;
-  return {grid, split};
-}
-
 }  // namespace
 
 void launch_fill_counts(hipStream_t s, const uint32_t* flag, int32_t* counts, int32_t value, int64_t n) {

@@ -1,5 +1,5 @@
-// Launchers for the gfx950 kernels (reduce.hip, counts.hip, pack_bf16.hip,
-// colsum.hip, xent.hip).
+// Launchers for the gfx950 kernels (reduce.hip, counts.hip, optim.hip,
+// pack_bf16.hip, colsum.hip, xent.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,6 +31,32 @@ void launch_count_expand(hipStream_t s, int32_t* out, const int32_t* counts, int
 void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t* counts, int64_t S, int64_t step,
                        int32_t N, int64_t C, int32_t kmax, DType dt, DType src_dt, bool axpy = false,
                        float alpha = 0.f, void* shadow = nullptr);
+// The fused optimizer step over a round's output (optim.hip).  Per element
+// g = src / per-chunk count, times min(1, max_norm / (sqrt(*sq) + 1e-6)) when
+// `sq` is given, then torch.optim.SGD's update (momentum, dampening 0) or
+// torch.optim.AdamW's on fp32 p, m (and v); bf16(p_new) into `shadow` if
+// given.  A chunk whose count is 0 is missing: p, m, v, shadow stay as they
+// are.  `t`: the step, one int32 on the device (AdamW's bias corrections).
+// src_dt: F32 or BF16.  nt: nontemporal instead of plain accesses (slower
+// where measured; for the comparison in bench/fused_opt.py).
+enum class OptimKind : int32_t { SGD = 0, AdamW = 1 };
+struct OptimSpec {
+  OptimKind kind = OptimKind::SGD;
+  double lr = 0, weight_decay = 0;
+  double momentum = 0;  // SGD
+  bool nesterov = false;
+  double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;  // AdamW
+  double max_norm = 0;                            // used with sq
+};
+void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
+                        const int32_t* counts, int64_t S, int64_t step, int32_t N, int64_t C, int32_t kmax,
+                        const OptimSpec& o, const int32_t* t, const float* sq, bool nt = false);
+// sq[0] = sum over the elements whose count is > 0 of (src / count)^2.  part:
+// fp32 [count_sqnorm_partials()] workspace; ticket: one uint32 zeroed once
+// (each launch leaves it zero again).  Deterministic for a given shape.
+void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const int32_t* counts, int64_t S,
+                         int64_t step, int32_t N, int64_t C, int32_t kmax, float* part, uint32_t* ticket);
+int32_t count_sqnorm_partials();
 // q (bf16) = rne(g + r), r = (g + r) - float(q) in place; r may be null (a
 // plain cast).  r becomes 0 where the sum or its rounding is not finite.
 void launch_pack_bf16(hipStream_t s, void* q, const float* g, float* r, int64_t n);

@@ -21,6 +21,23 @@ inline void check_launch(const char* what) {
   if (e != hipSuccess) throw AkkaError(std::string("akka: ") + what + ": " + hipGetErrorString(e));
 }
 
+// Workgroups of a region walk (the kernels over per-(block, chunk) counts):
+// one per region up to max_grid, and `split` workgroups sharing a region
+// (gridDim.y) while there are few regions and a region has the vectors to
+// keep them busy.
+struct RegionGrid {
+  int grid, split;
+};
+inline RegionGrid region_grid(int64_t regions, int64_t S, int64_t max_grid) {
+  const int grid = int(regions < max_grid ? regions : max_grid);
+  int split = int(max_grid / grid);
+  const int64_t per_region_vecs = (S / regions) / 4 + 1;
+  const int64_t useful = (per_region_vecs + kBlock - 1) / kBlock;
+  if (split > useful) split = int(useful);
+  if (split < 1) split = 1;
+  return {grid, split};
+}
+
 // Calls f(std::integral_constant<int, K>{}) for the K among Ks that equals n;
 // false (f not called) when none does.  One fold over ||: it stops at the
 // first K == n; `(f(...), true)` is the built-in comma, so f may return void.

@@ -1,0 +1,382 @@
+// gfx950 kernels of the fused optimizer step over a round's output: momentum
+// SGD and AdamW straight from the reduced sum and its per-(block, chunk)
+// contributor counts, with an optional global-norm clip.
+//
+// count_optim: one pass.  Per element g = sum / count(chunk), scaled by the
+// clip coefficient, then torch's update (torch.optim.SGD with dampening 0,
+// torch.optim.AdamW), operation by operation in the order and with the
+// roundings of torch's own element-wise kernels (update_one below), so torch
+// in fp32 is a comparator that differs in the last bits only.  p, m, v are
+// fp32; the sum is fp32 or bf16 (a compressed wire's sum, read wide into
+// fp32); an optional bf16 shadow receives bf16(p_new) from the same pass.
+//
+// Count 0 means MISSING, not zero: a chunk no contributor reached leaves p, m,
+// v and the shadow untouched -- the region is skipped before any load.  With
+// plain SGD a missing gradient and a zero gradient give the same parameters;
+// with momentum or Adam they do not (m would decay and still move p, v would
+// decay), and a parameter must not drift on stale momentum because a
+// threshold round dropped its chunk.  The bias corrections use the GLOBAL
+// step t (read from device memory: a captured step advances it on every
+// replay), also for a chunk that missed earlier steps: its m and v are then
+// older than t says, which only shortens its next steps.
+//
+// Region walk as count_mean (counts.hip): one workgroup per (block, chunk)
+// region at a time, the count a wave-uniform scalar, gridDim.y workgroups
+// sharing a region while there are few.  A unit is 8 elements: one 16-B
+// vector of a bf16 sum or two of an fp32 one, two each of p, m and v, one of
+// the shadow -- every stream moves 16 B per access.  Elements of a region
+// outside its 8-aligned body go through the scalar path.  Two units per
+// thread, every load of both in flight before the first store.
+//
+// Cache policy.  Bytes per element (fp32 sum; 2 less from a bf16 one):
+// SGD 20 (+2 shadow), AdamW 28 (+2 shadow).  At the config-5 bucket (41.75 M
+// elements, 0.75-1.25 GB per pass, far past the 256 MiB Infinity Cache) plain
+// loads and stores measured 4.7-5.3 TB/s of these bytes and nontemporal ones
+// 2.7-4.2 TB/s in every variant (AdamW + shadow from an fp32 sum: 237 us
+// against 309 us), so unlike pack_bf16 this pass uses plain accesses at every
+// size; `nt` is kept so that bench/fused_opt.py can repeat the comparison
+// (table in profiles/r08/fused_opt/README.md).
+//
+// count_sqnorm: sq[0] = sum over count > 0 of (sum / count)^2, the squared
+// global norm of the mean gradient the clip needs.  fp32 partials per thread,
+// a fixed wave + workgroup tree, one partial per workgroup written through
+// (sc0 sc1) into a workspace; the last workgroup to draw the ticket sums the
+// partials in index order and re-arms the ticket (the colsum / xent hand-off:
+// no float atomics, no waits).  Same bits for the same shape on every call,
+// and nothing to reset between the replays of a graph.
+#include <hip/hip_runtime.h>
+
+#include "elem.h"
+#include "kernels.h"
+#include "launch_util.h"
+#include "xgmi_device.h"
+
+namespace akka {
+
+namespace {
+
+// Host-rounded scalars of one step (each the fp32 torch's kernels receive).
+struct OptimK {
+  float neg_lr, wd, mu;  // SGD
+  int32_t nesterov;
+  float lr, decay, b1, w1, b2, w2, eps;  // AdamW: decay = 1 - lr * wd, w_k = 1 - b_k
+  float max_norm;
+};
+
+// Wave-uniform values read from device memory when the kernel runs.
+struct Coef {
+  float clip;    // gradient scale
+  float d1, d2;  // AdamW: p += m / (sqrt(v) / d1 + d2)
+};
+
+template <bool ADAM>
+__device__ __forceinline__ Coef coefficients(const OptimK& k, const int32_t* t, const float* sq) {
+#pragma clang fp contract(off)
+  Coef c{1.f, 0.f, 0.f};
+  // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)), the quotient as reciprocal * max_norm
+  if (sq) c.clip = fminf(1.f, (1.f / (sqrtf(*sq) + 1e-6f)) * k.max_norm);
+  if constexpr (ADAM) {
+    // AdamW(capturable=True): bc_k = 1 - b_k^t in fp32; the step size lr / bc1
+    // and sqrt(bc2) folded into the denominator, eps scaled to match:
+    // p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+    const float tf = float(*t);
+    const float nss = -((1.f / (1.f - powf(k.b1, tf))) * k.lr);
+    c.d1 = sqrtf(1.f - powf(k.b2, tf)) * nss;
+    c.d2 = (1.f / nss) * k.eps;
+  }
+  return c;
+}
+
+// One element.  No contraction but the fused multiply-adds spelled out: they
+// are the ones torch's add(alpha) / lerp / addcmul kernels make.
+template <bool ADAM>
+__device__ __forceinline__ void update_one(float g, float& p, float& m, float& v, const OptimK& k, const Coef& c) {
+#pragma clang fp contract(off)
+  g = g * c.clip;
+  if constexpr (ADAM) {
+    p = p * k.decay;
+    const float d = g - m;  // m = b1 * m + (1 - b1) * g as lerp_ spells it
+    m = k.w1 < 0.5f ? __builtin_fmaf(k.w1, d, m) : __builtin_fmaf(-d, 1.f - k.w1, g);
+    v = __builtin_fmaf(k.w2, g * g, v * k.b2);
+    p = p + m / (sqrtf(v) / c.d1 + c.d2);
+  } else {
+    g = __builtin_fmaf(k.wd, p, g);
+    m = m * k.mu + g;
+    if (k.nesterov) g = __builtin_fmaf(k.mu, m, g);
+    else g = m;
+    p = __builtin_fmaf(k.neg_lr, g, p);
+  }
+}
+
+template <typename TS, bool ADAM, bool SHADOW, bool NT>
+__global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__ p, float* __restrict__ m,
+                                                             float* __restrict__ v, bf16_t* __restrict__ shadow,
+                                                             const TS* __restrict__ src,
+                                                             const int32_t* __restrict__ counts, int64_t S,
+                                                             int64_t step, int32_t N, int64_t C, int32_t kmax,
+                                                             OptimK k, const int32_t* __restrict__ t,
+                                                             const float* __restrict__ sq) {
+  constexpr int E = 8;                        // elements per unit
+  constexpr int ES = Elt<TS>::kPerVec;        // elements per source vector
+  constexpr int NS = E / ES;                  // source vectors per unit
+  constexpr int NF = E / Elt<float>::kPerVec; // fp32 vectors per unit and stream
+  const Coef c = coefficients<ADAM>(k, t, sq);
+  const int64_t nregions = int64_t(N) * kmax;
+  for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
+    const int32_t j = int32_t(reg / kmax);
+    const int64_t kk = reg - int64_t(j) * kmax;
+    const int64_t bs = j * step < S ? j * step : S;
+    const int64_t be = j >= N - 1 ? S : ((j + 1) * step < S ? (j + 1) * step : S);
+    const int64_t s = bs + kk * C;
+    if (s >= be) continue;
+    const int64_t e = s + C < be ? s + C : be;
+    const int32_t cnt = counts[reg];
+    if (cnt <= 0) continue;  // missing: nothing of this region is loaded or stored
+    const float fv = float(cnt);
+    int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first element 16-B aligned in every stream
+    if (a > e) a = e;
+    const int64_t nv = (e - a) / E;
+    auto one = [&](int64_t i) {
+      float pi = p[i], mi = m[i], vi = ADAM ? v[i] : 0.f;
+      update_one<ADAM>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
+      p[i] = pi;
+      m[i] = mi;
+      if constexpr (ADAM) v[i] = vi;
+      if constexpr (SHADOW) shadow[i] = Elt<bf16_t>::from_f(pi);
+    };
+    if (blockIdx.y == 0) {
+      for (int64_t i = s + threadIdx.x; i < a; i += kBlock) one(i);
+      for (int64_t i = a + nv * E + threadIdx.x; i < e; i += kBlock) one(i);
+    }
+    const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
+    v4u* p4 = reinterpret_cast<v4u*>(p + a);
+    v4u* m4 = reinterpret_cast<v4u*>(m + a);
+    v4u* v4 = reinterpret_cast<v4u*>(v + a);
+    v4u* h4 = reinterpret_cast<v4u*>(shadow + a);
+    auto ld = [](const v4u* q) { return NT ? __builtin_nontemporal_load(q) : *q; };
+    auto st = [](const v4u& x, v4u* q) {
+      if constexpr (NT) __builtin_nontemporal_store(x, q);
+      else *q = x;
+    };
+    struct Unit {
+      v4u s[NS], p[NF], m[NF], v[NF];
+    };
+    auto load = [&](int64_t at) {
+      Unit u;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) u.s[q] = ld(s4 + at * NS + q);
+#pragma unroll
+      for (int q = 0; q < NF; ++q) u.p[q] = ld(p4 + at * NF + q);
+#pragma unroll
+      for (int q = 0; q < NF; ++q) u.m[q] = ld(m4 + at * NF + q);
+      if constexpr (ADAM) {
+#pragma unroll
+        for (int q = 0; q < NF; ++q) u.v[q] = ld(v4 + at * NF + q);
+      }
+      return u;
+    };
+    auto update = [&](Unit& u, int64_t at) {
+      float g[E], pn[E];
+#pragma unroll
+      for (int q = 0; q < E; ++q) g[q] = 0.f;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) Elt<TS>::add(reinterpret_cast<float(&)[ES]>(g[q * ES]), u.s[q]);
+#pragma unroll
+      for (int q = 0; q < E; ++q) {
+        float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = __uint_as_float(u.m[q >> 2][q & 3]);
+        float vi = ADAM ? __uint_as_float(u.v[q >> 2][q & 3]) : 0.f;
+        update_one<ADAM>(g[q] / fv, pi, mi, vi, k, c);
+        pn[q] = pi;
+        u.p[q >> 2][q & 3] = __float_as_uint(pi);
+        u.m[q >> 2][q & 3] = __float_as_uint(mi);
+        if constexpr (ADAM) u.v[q >> 2][q & 3] = __float_as_uint(vi);
+      }
+#pragma unroll
+      for (int q = 0; q < NF; ++q) {
+        st(u.p[q], p4 + at * NF + q);
+        st(u.m[q], m4 + at * NF + q);
+        if constexpr (ADAM) st(u.v[q], v4 + at * NF + q);
+      }
+      if constexpr (SHADOW) st(Elt<bf16_t>::pack(pn), h4 + at);
+    };
+    const int64_t stride = int64_t(kBlock) * gridDim.y;
+    int64_t i = int64_t(blockIdx.y) * kBlock + threadIdx.x;
+    for (; i + stride < nv; i += 2 * stride) {
+      Unit u0 = load(i), u1 = load(i + stride);
+      update(u0, i);
+      update(u1, i + stride);
+    }
+    for (; i < nv; i += stride) {
+      Unit u = load(i);
+      update(u, i);
+    }
+  }
+}
+
+// Sum over the workgroup in a fixed order: xor tree in the wave, waves in order.
+__device__ __forceinline__ float block_sum(float x, float* red) {
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  __syncthreads();  // red may still be read by a previous sum
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  float r = red[0];
+  for (int w = 1; w < kBlock / 64; ++w) r += red[w];
+  return r;
+}
+
+constexpr int kSqUnroll = 4;
+
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void count_sqnorm_kernel(float* __restrict__ sq, const TS* __restrict__ src,
+                                                              const int32_t* __restrict__ counts, int64_t S,
+                                                              int64_t step, int32_t N, int64_t C, int32_t kmax,
+                                                              float* __restrict__ part,
+                                                              uint32_t* __restrict__ ticket) {
+  constexpr int E = Elt<TS>::kPerVec;
+  __shared__ float red[kBlock / 64 + 1];
+  float acc = 0.f;
+  const int64_t nregions = int64_t(N) * kmax;
+  for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
+    const int32_t j = int32_t(reg / kmax);
+    const int64_t kk = reg - int64_t(j) * kmax;
+    const int64_t bs = j * step < S ? j * step : S;
+    const int64_t be = j >= N - 1 ? S : ((j + 1) * step < S ? (j + 1) * step : S);
+    const int64_t s = bs + kk * C;
+    if (s >= be) continue;
+    const int64_t e = s + C < be ? s + C : be;
+    const int32_t cnt = counts[reg];
+    if (cnt <= 0) continue;
+    const float fv = float(cnt);
+    int64_t a = (s + E - 1) & ~int64_t(E - 1);
+    if (a > e) a = e;
+    const int64_t nv = (e - a) / E;
+    auto one = [&](int64_t i) {
+      const float g = Elt<TS>::to_f(src[i]) / fv;
+      acc += g * g;
+    };
+    if (blockIdx.y == 0) {
+      for (int64_t i = s + threadIdx.x; i < a; i += kBlock) one(i);
+      for (int64_t i = a + nv * E + threadIdx.x; i < e; i += kBlock) one(i);
+    }
+    const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
+    auto vec = [&](const v4u& sv) {
+      float g[E];
+#pragma unroll
+      for (int q = 0; q < E; ++q) g[q] = 0.f;
+      Elt<TS>::add(g, sv);
+#pragma unroll
+      for (int q = 0; q < E; ++q) {
+        const float x = g[q] / fv;
+        acc += x * x;
+      }
+    };
+    constexpr int U = kSqUnroll;
+    const int64_t stride = int64_t(kBlock) * gridDim.y;
+    int64_t i = int64_t(blockIdx.y) * kBlock + threadIdx.x;
+    for (; i + (U - 1) * stride < nv; i += U * stride) {
+      v4u sv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) sv[u] = s4[i + u * stride];
+#pragma unroll
+      for (int u = 0; u < U; ++u) vec(sv[u]);
+    }
+    for (; i < nv; i += stride) vec(s4[i]);
+  }
+  acc = block_sum(acc, red);
+  const uint32_t nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;
+  const auto rs = xgmi::sys_rsrc(part, int64_t(nwg) * 4);
+  if (threadIdx.x == 0) {
+    // the workgroup's partial, written through for the last arriver
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc), rs, int(wg * 4), 0, xgmi::kSysAux);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    red[kBlock / 64] =
+        __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nwg - 1 ? 1.f : 0.f;
+  }
+  __syncthreads();
+  if (red[kBlock / 64] == 0.f) return;
+  // last workgroup: the partials in index order per thread, then the fixed tree
+  float sum = 0.f;
+  for (uint32_t i = threadIdx.x; i < nwg; i += kBlock)
+    sum += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, int(i * 4), 0, xgmi::kSysAux));
+  sum = block_sum(sum, red);
+  if (threadIdx.x == 0) {
+    sq[0] = sum;
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
+  }
+}
+
+bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+}  // namespace
+
+void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
+                        const int32_t* counts, int64_t S, int64_t step, int32_t N, int64_t C, int32_t kmax,
+                        const OptimSpec& o, const int32_t* t, const float* sq, bool nt) {
+  if (S <= 0) return;
+  const bool adam = o.kind == OptimKind::AdamW;
+  AKKA_CHECK(p && m && src && counts && (!adam || (v && t)), "count_optim: null buffer");
+  AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
+             "count_optim: buffers must be 16-B aligned");
+  AKKA_CHECK(int64_t(N) * kmax > 0 && step >= 0 && C > 0, "count_optim: bad geometry");
+  OptimK k{};
+  k.neg_lr = float(-o.lr);
+  k.wd = float(o.weight_decay);
+  k.mu = float(o.momentum);
+  k.nesterov = o.nesterov ? 1 : 0;
+  k.lr = float(o.lr);
+  k.decay = float(1.0 - o.lr * o.weight_decay);
+  k.b1 = float(o.beta1);
+  k.w1 = float(1.0 - o.beta1);
+  k.b2 = float(o.beta2);
+  k.w2 = float(1.0 - o.beta2);
+  k.eps = float(o.eps);
+  k.max_norm = float(o.max_norm);
+  const auto [grid, split] = region_grid(int64_t(N) * kmax, S, kMaxGrid);
+  auto* h = static_cast<bf16_t*>(shadow);
+#define AKKA_OPT(TS, AD, SH, NTV)                                                                              \
+  hipLaunchKernelGGL((count_optim_kernel<TS, AD, SH, NTV>), dim3(grid, split), dim3(kBlock), 0, s, p, m, v, h, \
+                     static_cast<const TS*>(src), counts, S, step, N, C, kmax, k, t, sq)
+#define AKKA_OPT_NT(TS, AD, SH)       \
+  do {                                \
+    if (nt) AKKA_OPT(TS, AD, SH, true); \
+    else AKKA_OPT(TS, AD, SH, false); \
+  } while (0)
+#define AKKA_OPT_SH(TS, AD)                \
+  do {                                     \
+    if (shadow) AKKA_OPT_NT(TS, AD, true); \
+    else AKKA_OPT_NT(TS, AD, false);       \
+  } while (0)
+  if (src_dt == DType::BF16) {
+    if (adam) AKKA_OPT_SH(bf16_t, true);
+    else AKKA_OPT_SH(bf16_t, false);
+  } else {
+    if (adam) AKKA_OPT_SH(float, true);
+    else AKKA_OPT_SH(float, false);
+  }
+#undef AKKA_OPT_SH
+#undef AKKA_OPT_NT
+#undef AKKA_OPT
+  check_launch("count_optim");
+}
+
+int32_t count_sqnorm_partials() { return kMaxGrid; }
+
+void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const int32_t* counts, int64_t S,
+                         int64_t step, int32_t N, int64_t C, int32_t kmax, float* part, uint32_t* ticket) {
+  if (S <= 0) return;
+  AKKA_CHECK(sq && src && counts && part && ticket, "count_sqnorm: null buffer");
+  AKKA_CHECK(aligned16(src), "count_sqnorm: the sum must be 16-B aligned");
+  AKKA_CHECK(int64_t(N) * kmax > 0 && step >= 0 && C > 0, "count_sqnorm: bad geometry");
+  // grid * split <= kMaxGrid: one partial each in `part`
+  const auto [grid, split] = region_grid(int64_t(N) * kmax, S, kMaxGrid);
+  // plain loads: the update pass reads the sum next
+#define AKKA_SQ(TS)                                                                                          \
+  hipLaunchKernelGGL((count_sqnorm_kernel<TS>), dim3(grid, split), dim3(kBlock), 0, s, sq,                   \
+                     static_cast<const TS*>(src), counts, S, step, N, C, kmax, part, ticket)
+  if (src_dt == DType::BF16) AKKA_SQ(bf16_t);
+  else AKKA_SQ(float);
+#undef AKKA_SQ
+  check_launch("count_sqnorm");
+}
+
+}  // namespace akka

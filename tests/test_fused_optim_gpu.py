@@ -1,0 +1,287 @@
+"""The fused optimizer pass on the GPU (``optim.hip``: ``count_optim`` and
+``count_sqnorm``) against torch's optimizers.
+
+Numerics: from the same fp32 inputs, torch's optimizer in float64 is the
+reference and torch's optimizer in fp32 on the GPU (``foreach=False``; AdamW
+``capturable=True``) the comparator; the gradient of both is
+``out.mean(dtype=torch.float32)`` (the ``count_mean`` kernel).  The kernel's
+worst error against the reference may be at most 4x the comparator's, for p,
+m and v, after 1 step and after 20, over every element.  Elements of count-0
+chunks keep parameters and state in all three runs (the torch runs put them
+back after each step).  Every case prints its ratios before it asserts;
+profiles/r08/fused_opt/README.md holds the measured ones."""
+import functools
+import math
+
+import pytest
+import torch
+
+from akka_allreduce_amd.data import AllReduceOutput, Geometry, sqnorm_workspace
+
+pytestmark = pytest.mark.gpu
+
+# the smallest shapes that reach each path of the region walk: one element; regions shorter than a unit (all head
+# and tail); unaligned regions, no multiple of 4 or 8; few regions, so several workgroups share one (gridDim.y > 1)
+# and run the unrolled loop and its remainder; many regions with bodies, heads and tails
+SHAPES = [(1, 1, 1), (7, 3, 2), (1003, 4, 67), (300_001, 2, 150_000), (1_000_003, 4, 4099)]
+STEPS = (1, 20)
+NGRAD = 4
+HYPER = {
+    "sgd": dict(lr=0.05, momentum=0.9, nesterov=False, weight_decay=1e-2),
+    "nesterov": dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-2),
+    "adamw": dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01),
+}
+M_SENTINEL, V_SENTINEL, H_SENTINEL = 123.25, 77.5, -3.5
+
+
+def _dev():
+    return torch.device("cuda", 0)
+
+
+@functools.lru_cache(maxsize=2)
+def _inputs(S, N, C, src):
+    """Counts (random in [0, N], one chunk forced to 0 and one to N), NGRAD
+    sums of the source dtype with their fp32 means, and the initial state with
+    sentinels in the count-0 elements."""
+    dev = _dev()
+    geo = Geometry(S, N, C)
+    g = torch.Generator(device="cpu").manual_seed(S * 31 + N)
+    pc = torch.randint(0, N + 1, (N, geo.kmax), dtype=torch.int32, generator=g)
+    pc[0, 0] = 0
+    pc[N - 1, 0] = N
+    count = geo.expand_counts(pc).to(dev)
+    pc = pc.to(dev)
+    missing = count == 0
+    sums, means = [], []
+    for i in range(NGRAD):
+        base = torch.randn(S, generator=g).to(dev)
+        if i == 2:
+            base = base * 1e-2  # a round whose norm is below max_norm: the clip coefficient clamps to 1
+        # count-0 elements keep a non-zero sum: it must not be read
+        s = torch.where(missing, base, base * count).to(torch.bfloat16 if src == "bf16" else torch.float32)
+        sums.append(s)
+        means.append(AllReduceOutput(s, counts_per_chunk=pc, geometry=geo).mean(dtype=torch.float32).clone()
+                     if src == "bf16" else AllReduceOutput(s, counts_per_chunk=pc, geometry=geo).mean().clone())
+    p0 = torch.randn(S, generator=g).to(dev)
+    m0 = torch.where(missing, torch.full_like(p0, M_SENTINEL), torch.zeros_like(p0))
+    v0 = torch.where(missing, torch.full_like(p0, V_SENTINEL), torch.zeros_like(p0))
+    torch.cuda.synchronize()
+    return dict(geo=geo, pc=pc, count=count, missing=missing, sums=sums, means=means, p0=p0, m0=m0, v0=v0,
+                max_norm=0.1 * math.sqrt(S))
+
+
+def _torch_run(kind, inp, dtype, clip):
+    """torch's optimizer on the means, count-0 elements put back after every
+    step; (p, m, v) snapshots at STEPS."""
+    h = HYPER[kind]
+    p = torch.nn.Parameter(inp["p0"].to(dtype).clone())
+    m, v = inp["m0"].to(dtype).clone(), inp["v0"].to(dtype).clone()
+    if kind == "adamw":
+        cap = dtype == torch.float32  # the float64 reference keeps the step (and the bias corrections) in double
+        opt = torch.optim.AdamW([p], lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
+                                foreach=False, capturable=cap)
+        step = torch.zeros((), dtype=torch.float32, device=p.device if cap else "cpu")
+        opt.state[p] = {"step": step, "exp_avg": m, "exp_avg_sq": v}
+    else:
+        opt = torch.optim.SGD([p], lr=h["lr"], momentum=h["momentum"], nesterov=h["nesterov"],
+                              weight_decay=h["weight_decay"], foreach=False)
+        opt.state[p] = {"momentum_buffer": m}
+    missing = inp["missing"]
+    snaps = {}
+    for s in range(max(STEPS)):
+        p.grad = inp["means"][s % NGRAD].to(dtype).clone()
+        if clip:
+            torch.nn.utils.clip_grad_norm_([p], inp["max_norm"], foreach=False)
+        prev = [x.detach().clone() for x in (p, m, v)]
+        opt.step()
+        with torch.no_grad():
+            for x, x0 in zip((p, m, v), prev):
+                x.copy_(torch.where(missing, x0, x))
+        if s + 1 in STEPS:
+            snaps[s + 1] = tuple(x.detach().clone() for x in (p, m, v))
+    return snaps
+
+
+@functools.lru_cache(maxsize=2)
+def _references(S, N, C, src, kind, clip):
+    inp = _inputs(S, N, C, src)
+    r = _torch_run(kind, inp, torch.float64, clip), _torch_run(kind, inp, torch.float32, clip)
+    torch.cuda.synchronize()
+    return r
+
+
+def _kernel_state(inp, shadow):
+    p, m, v = inp["p0"].clone(), inp["m0"].clone(), inp["v0"].clone()
+    t = torch.zeros(1, dtype=torch.int32, device=p.device)
+    sh = torch.full_like(p, H_SENTINEL, dtype=torch.bfloat16) if shadow else None
+    return p, m, v, t, sh
+
+
+def _step(inp, kind, state, i, ws):
+    p, m, v, t, sh = state
+    h = dict(HYPER[kind])
+    lr = h.pop("lr")
+    out = AllReduceOutput(inp["sums"][i % NGRAD], counts_per_chunk=inp["pc"], geometry=inp["geo"])
+    t.add_(1)
+    out.optim_step_("adamw" if kind == "adamw" else "sgd", p, m, v if kind == "adamw" else None, t, lr, shadow=sh,
+                    max_norm=inp["max_norm"] if ws is not None else None, norm_ws=ws, **h)
+
+
+# the topmost parameter varies fastest: both shadow cases share one reference, every case of a shape its inputs
+@pytest.mark.parametrize("shadow", [False, True])
+@pytest.mark.parametrize("clip", [False, True])
+@pytest.mark.parametrize("kind", ["sgd", "nesterov", "adamw"])
+@pytest.mark.parametrize("src", ["fp32", "bf16"])
+@pytest.mark.parametrize("S,N,C", SHAPES)
+def test_update_matches_torch(shadow, clip, kind, src, S, N, C):
+    inp = _inputs(S, N, C, src)
+    ref64, ref32 = _references(S, N, C, src, kind, clip)
+    missing = inp["missing"]
+    assert bool(missing.any()) or N == 1
+    state = _kernel_state(inp, shadow)
+    ws = sqnorm_workspace(_dev()) if clip else None
+    p, m, v, t, sh = state
+    failures = []
+    for i in range(max(STEPS)):
+        _step(inp, kind, state, i, ws)
+        if i + 1 not in STEPS:
+            continue
+        torch.cuda.synchronize()
+        # count-0 regions: bitwise what they were
+        assert torch.equal(p[missing], inp["p0"][missing])
+        assert bool((m[missing] == M_SENTINEL).all())
+        if kind == "adamw":
+            assert bool((v[missing] == V_SENTINEL).all())
+        else:
+            assert torch.equal(v, inp["v0"])  # SGD has no second moment: untouched everywhere
+        if shadow:
+            assert bool((sh[missing].float() == H_SENTINEL).all())
+            assert torch.equal(sh[~missing], p[~missing].to(torch.bfloat16))
+        assert int(t) == i + 1
+        for name, got, r64, r32 in zip("pmv", (p, m, v), ref64[i + 1], ref32[i + 1]):
+            err = float((got.double() - r64).abs().max())
+            cmp_err = float((r32.double() - r64).abs().max())
+            ratio = err / cmp_err if cmp_err > 0 else (0.0 if err == 0 else math.inf)
+            print(f"RATIO S={S} src={src} kind={kind} clip={int(clip)} shadow={int(shadow)} step={i + 1} {name} "
+                  f"kernel={err:.3e} torch32={cmp_err:.3e} ratio={ratio:.3f}")
+            if not err <= 4 * cmp_err:
+                failures.append((i + 1, name, err, cmp_err))
+    assert not failures, failures
+
+
+@pytest.mark.parametrize("S,N,C", SHAPES)
+@pytest.mark.parametrize("src", ["fp32", "bf16"])
+def test_sqnorm_matches_float64_and_is_deterministic(src, S, N, C):
+    inp = _inputs(S, N, C, src)
+    ws = sqnorm_workspace(_dev())
+    out = AllReduceOutput(inp["sums"][0], counts_per_chunk=inp["pc"], geometry=inp["geo"])
+    got = [out.sqnorm(ws).clone() for _ in range(3)]
+    c = inp["count"].double()
+    mean64 = torch.where(c > 0, inp["sums"][0].double() / c.clamp(min=1), torch.zeros_like(c))
+    want = float((mean64 * mean64).sum())
+    torch.cuda.synchronize()
+    # non-negative terms, add chains < 100 long: relative error <= 100 * 2**-24 < 1e-5
+    assert abs(float(got[0]) - want) <= 1e-5 * want, (float(got[0]), want)
+    assert torch.equal(got[0], got[1]) and torch.equal(got[0], got[2])  # the ticket re-arms
+    assert float(ws[1]) == 0.0
+
+
+def test_all_chunks_missing_is_a_no_op():
+    S, N, C = 1003, 4, 67
+    inp = _inputs(S, N, C, "fp32")
+    pc = torch.zeros_like(inp["pc"])
+    p, m, v, t, sh = _kernel_state(inp, True)
+    ws = sqnorm_workspace(_dev())
+    t.add_(1)
+    out = AllReduceOutput(inp["sums"][0], counts_per_chunk=pc, geometry=inp["geo"])
+    out.optim_step_("adamw", p, m, v, t, 1e-3, shadow=sh, max_norm=1.0, norm_ws=ws)
+    torch.cuda.synchronize()
+    assert float(ws[0]) == 0.0
+    assert torch.equal(p, inp["p0"]) and torch.equal(m, inp["m0"]) and torch.equal(v, inp["v0"])
+    assert bool((sh.float() == H_SENTINEL).all())
+
+
+def test_cuda_tensors_never_fall_back():
+    inp = _inputs(1003, 4, 67, "fp32")
+    out = AllReduceOutput(inp["sums"][0], counts_per_chunk=inp["pc"], geometry=inp["geo"])
+    base = torch.zeros(1003 + 1, device=_dev())
+    m, t = torch.zeros(1003, device=_dev()), torch.ones(1, dtype=torch.int32, device=_dev())
+    with pytest.raises(ValueError, match="aligned"):
+        out.optim_step_("sgd", base[1:], m, None, t, 0.1)  # p is not 16-B aligned
+    _ = out.count  # per-element counts expanded: the fused conditions of axpy_mean_ no longer hold
+    with pytest.raises(ValueError, match="fused pass"):
+        out.optim_step_("sgd", base[:1003], m, None, t, 0.1)
+
+
+@pytest.mark.parametrize("src", ["fp32", "bf16"])
+def test_graph_replay_of_the_adamw_pass(src):
+    """t.add_(1), the norm pass and the update captured once: three replays
+    are three steps (the step counter is on the device, the norm workspace
+    re-arms itself), bitwise the three eager calls from the same start."""
+    S, N, C = 300_001, 2, 150_000
+    inp = _inputs(S, N, C, src)
+    dev = _dev()
+    eager = _kernel_state(inp, True)
+    ws_e = sqnorm_workspace(dev)
+    for _ in range(3):
+        _step(inp, "adamw", eager, 0, ws_e)
+    graphed = _kernel_state(inp, True)
+    ws_g = sqnorm_workspace(dev)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        _step(inp, "adamw", graphed, 0, ws_g)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    for x, x0 in zip(graphed[:3], (inp["p0"], inp["m0"], inp["v0"])):
+        assert torch.equal(x, x0)  # capturing ran nothing
+    assert int(graphed[3]) == 0
+    for _ in range(3):
+        graph.replay()
+    torch.cuda.synchronize()
+    assert int(graphed[3]) == 3 and int(eager[3]) == 3
+    for name, a, b in zip(("p", "m", "v", "t", "shadow"), eager, graphed):
+        assert torch.equal(a, b), name
+    assert torch.equal(ws_e[:2], ws_g[:2])
+
+
+def _mlp_run(graphed, wire, steps=5):
+    from akka_allreduce_amd.models.mlp import MLP, GraphedDPStep, dp_sgd_step, synthetic_batch
+    from akka_allreduce_amd.parallel import FusedAdamW, ThresholdAllreduce
+    from akka_allreduce_amd.parallel.dp import GradientBucket
+
+    dev = _dev()
+    gen = torch.Generator(device=dev).manual_seed(5)
+    batches = [synthetic_batch(32, 64, 10, device=dev, generator=gen) for _ in range(steps)]
+    torch.manual_seed(0)
+    model = MLP(64, 128, 10).to(dev)
+    bucket = GradientBucket(list(model.parameters()), flatten_params=True,
+                            wire_dtype=torch.bfloat16 if wire else None)
+    opt = FusedAdamW(bucket, weight_decay=0.01, max_grad_norm=1.0)
+    ar = ThresholdAllreduce(bucket.numel, max_chunk_size=4096, device=dev,
+                            **({"dtype": torch.bfloat16} if wire else {}))
+    if graphed:
+        step = GraphedDPStep(model, bucket, *batches[0], compute_dtype=torch.bfloat16, optimizer=opt)
+        assert int(opt.t) == 0  # warmup and capture ran forward + backward only
+        losses = [float(step(x, y, 1e-2, ar)) for x, y in batches]
+        keep = opt.m
+        opt.m = torch.zeros_like(keep)
+        with pytest.raises(RuntimeError, match="moved"):
+            step(*batches[0], 1e-2, ar)
+        opt.m = keep
+    else:
+        losses = [dp_sgd_step(model, x, y, 1e-2, ar, bucket, compute_dtype=torch.bfloat16, optimizer=opt)
+                  for x, y in batches]
+    torch.cuda.synchronize()
+    assert int(opt.t) == steps and bucket._shadow_on
+    return losses, bucket.pflat.clone(), bucket.sflat.clone(), opt.m.clone(), opt.v.clone()
+
+
+@pytest.mark.parametrize("wire", [False, True])
+def test_graphed_mlp_step_with_fused_adamw_matches_eager(wire):
+    eager = _mlp_run(False, wire)
+    graphed = _mlp_run(True, wire)
+    assert eager[0] == graphed[0], (eager[0], graphed[0])
+    for name, a, b in zip(("pflat", "sflat", "m", "v"), eager[1:], graphed[1:]):
+        assert torch.equal(a, b), name
+    assert torch.equal(graphed[2], graphed[1].to(torch.bfloat16))

@@ -65,6 +65,16 @@ class Geometry:
         return per_chunk.reshape(-1)[blk * self.kmax + k].to(torch.int32)
 
 
+DTYPE_NAME = {torch.float32: "float32", torch.bfloat16: "bfloat16"}  # the native module's dtype names
+
+
+def counts_table(per_chunk: torch.Tensor, g: Geometry) -> tuple:
+    """The counts-table argument of the native count passes, behind the contiguous counts tensor it points
+    into: hold that until the call returns."""
+    pc = per_chunk.contiguous()
+    return pc, (pc.data_ptr(), g.dataSize, g.step, g.workerNum, g.maxChunkSize, g.kmax)
+
+
 def sqnorm_workspace(device) -> torch.Tensor:
     """Workspace of ``AllReduceOutput.sqnorm`` (the global-norm clip of
     ``optim_step_``): the result, the kernel's ticket and one partial per
@@ -147,24 +157,27 @@ class AllReduceOutput:
                 self._count = self.geometry.expand_counts(self.counts_per_chunk)
         return self._count
 
-    def _fused_ok(self, dst: torch.Tensor, wide: bool = False) -> bool:
-        d, g = self.data, self.geometry
-        dt_ok = (d.dtype == torch.bfloat16 and dst.dtype == torch.float32) if wide else dst.dtype == d.dtype
-        return (d.is_cuda and d.dtype in (torch.float32, torch.bfloat16) and self.counts_per_chunk is not None
-                and g is not None and self._count is None and dst.is_contiguous() and dt_ok
-                and dst.device == d.device and dst.numel() == d.numel() and d.data_ptr() % 16 == 0
-                and dst.data_ptr() % 16 == 0)
+    def _feeds_count_pass(self) -> bool:
+        """Can this sum feed a native count pass (per-chunk counts not yet expanded, 16-B aligned)?"""
+        d = self.data
+        return (d.is_cuda and d.dtype in DTYPE_NAME and d.is_contiguous() and d.data_ptr() % 16 == 0
+                and self.counts_per_chunk is not None and self.geometry is not None and self._count is None)
+
+    def _flat_ok(self, t: torch.Tensor, dtype: torch.dtype, wide: bool = False, align: int = 16) -> bool:
+        """Can the flat tensor ``t`` be a destination, state or shadow of a count pass over this sum?
+        ``wide``: ``t`` takes the fp32 mean of a bf16 sum."""
+        d = self.data
+        return (t.dtype == dtype and (not wide or self._is_wide(dtype)) and t.is_contiguous()
+                and t.device == d.device and t.numel() == d.numel() and t.data_ptr() % align == 0)
 
     def _count_mean(self, dst: torch.Tensor, axpy: bool, alpha: float, shadow: Optional[torch.Tensor] = None) -> None:
         from ._native_loader import load
 
-        d, g = self.data, self.geometry
-        pc = self.counts_per_chunk.contiguous()
-        name = {torch.bfloat16: "bfloat16", torch.float32: "float32"}
-        load().count_mean(dst.data_ptr(), d.data_ptr(), pc.data_ptr(), g.dataSize, g.step, g.workerNum,
-                          g.maxChunkSize, g.kmax, name[dst.dtype],
+        d = self.data
+        pc, table = counts_table(self.counts_per_chunk, self.geometry)
+        load().count_mean(dst.data_ptr(), d.data_ptr(), table, DTYPE_NAME[dst.dtype],
                           torch.cuda.current_stream(d.device).cuda_stream, axpy, float(alpha),
-                          shadow.data_ptr() if shadow is not None else 0, name[d.dtype])
+                          shadow.data_ptr() if shadow is not None else 0, DTYPE_NAME[d.dtype])
 
     def _is_wide(self, dst_dtype: torch.dtype) -> bool:
         return self.data.dtype == torch.bfloat16 and dst_dtype == torch.float32
@@ -180,9 +193,8 @@ class AllReduceOutput:
         on the GPU, reading bf16 and writing fp32."""
         self.wait()
         wide = wide and self._is_wide(y.dtype)
-        if self._fused_ok(y, wide) and (shadow is None or (
-                y.dtype == torch.float32 and shadow.dtype == torch.bfloat16 and shadow.is_contiguous()
-                and shadow.numel() == y.numel() and shadow.device == y.device and shadow.data_ptr() % 16 == 0)):
+        if self._feeds_count_pass() and self._flat_ok(y, torch.float32 if wide else self.data.dtype, wide) and (
+                shadow is None or (y.dtype == torch.float32 and self._flat_ok(shadow, torch.bfloat16))):
             self._count_mean(y, True, alpha, shadow)
             return y
         m = self.mean(dtype=torch.float32) if wide else self.mean()
@@ -231,35 +243,29 @@ class AllReduceOutput:
             raise ValueError(f"optim_step_: a float32 or bfloat16 sum, not {d.dtype}")
         state =[("m", m)] + ([("v", v)] if adam else [])
         for name, s in [("p", p)] + state:
-            if s is None or s.dtype != torch.float32 or not s.is_contiguous() or s.numel() != d.numel() \
-                    or s.device != d.device:
+            if s is None or not self._flat_ok(s, torch.float32, align=1):
                 raise ValueError(f"optim_step_: {name} must be contiguous float32 of the round's size and device")
-        if shadow is not None and (shadow.dtype != torch.bfloat16 or not shadow.is_contiguous()
-                                   or shadow.numel() != p.numel() or shadow.device != p.device):
+        if shadow is not None and not self._flat_ok(shadow, torch.bfloat16, align=1):
             raise ValueError("optim_step_: shadow must be contiguous bfloat16 of p's size and device")
         if t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device:
             raise ValueError("optim_step_: t is one int32 on p's device")
         if max_norm is not None and norm_ws is None:
             raise ValueError("optim_step_: max_norm needs a norm workspace (sqnorm_workspace)")
         if d.is_cuda:
-            wide = self._is_wide(p.dtype)
-            if not (self._fused_ok(p, wide) and all(s.data_ptr() % 16 == 0 for _, s in state)
-                    and (shadow is None or shadow.data_ptr() % 16 == 0)):
+            if not (self._feeds_count_pass() and all(self._flat_ok(s, torch.float32) for _, s in [("p", p)] + state)
+                    and (shadow is None or self._flat_ok(shadow, torch.bfloat16))):
                 raise ValueError("optim_step_: the fused pass needs a float32 or bfloat16 sum with its per-chunk "
                                  "counts (not expanded) and 16-B aligned buffers")
             from ._native_loader import load
 
             sq = self.sqnorm(norm_ws) if max_norm is not None else None
-            g = self.geometry
-            pc = self.counts_per_chunk.contiguous()
+            pc, table = counts_table(self.counts_per_chunk, self.geometry)
             load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
-                               shadow.data_ptr() if shadow is not None else 0, d.data_ptr(),
-                               "bfloat16" if d.dtype == torch.bfloat16 else "float32", pc.data_ptr(), g.dataSize,
-                               g.step, g.workerNum, g.maxChunkSize, g.kmax, t.data_ptr(),
-                               sq.data_ptr() if sq is not None else 0, float(lr), float(weight_decay),
-                               float(momentum), bool(nesterov), float(betas[0]), float(betas[1]), float(eps),
-                               float(max_norm) if max_norm is not None else 0.0,
-                               torch.cuda.current_stream(d.device).cuda_stream, bool(nt))
+                               shadow.data_ptr() if shadow is not None else 0, d.data_ptr(), DTYPE_NAME[d.dtype],
+                               table, t.data_ptr(), sq.data_ptr() if sq is not None else 0,
+                               torch.cuda.current_stream(d.device).cuda_stream, bool(nt), lr=lr,
+                               weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, beta1=betas[0],
+                               beta2=betas[1], eps=eps, max_norm=max_norm if max_norm is not None else 0.0)
             return p
         # the same formulas as torch operations (count-0 elements keep everything)
         keep = (self.count <= 0).view_as(p)
@@ -303,17 +309,13 @@ class AllReduceOutput:
             from ._native_loader import load
 
             nat = load()
-            if not (d.dtype in (torch.float32, torch.bfloat16) and self.counts_per_chunk is not None
-                    and self.geometry is not None and d.is_contiguous() and d.data_ptr() % 16 == 0
-                    and ws.numel() >= 2 + nat.count_sqnorm_partials()):
+            if not (self._feeds_count_pass() and ws.numel() >= 2 + nat.count_sqnorm_partials()):
                 raise ValueError("sqnorm: needs a 16-B aligned float32 or bfloat16 sum with its per-chunk counts "
                                  "and a workspace from sqnorm_workspace")
-            g = self.geometry
-            pc = self.counts_per_chunk.contiguous()
+            pc, table = counts_table(self.counts_per_chunk, self.geometry)
             # [0]: the result, [1]: the ticket (zero bits), [2:]: one partial per workgroup
-            nat.count_sqnorm(ws.data_ptr(), d.data_ptr(), "bfloat16" if d.dtype == torch.bfloat16 else "float32",
-                             pc.data_ptr(), g.dataSize, g.step, g.workerNum, g.maxChunkSize, g.kmax,
-                             ws.data_ptr() + 8, ws.data_ptr() + 4, torch.cuda.current_stream(d.device).cuda_stream)
+            nat.count_sqnorm(ws.data_ptr(), d.data_ptr(), DTYPE_NAME[d.dtype], table, ws.data_ptr() + 8,
+                             ws.data_ptr() + 4, torch.cuda.current_stream(d.device).cuda_stream)
             return ws[:1]
         g = self.mean(dtype=torch.float32) if d.dtype != torch.float32 else self.mean()
         ws[0] = (g * g).sum()
@@ -336,7 +338,7 @@ class AllReduceOutput:
             if out is not None and out.dtype != dtype:
                 raise ValueError(f"mean: out must be {dtype}")
             dst = torch.empty(d.shape, dtype=dtype, device=d.device) if out is None else out
-            if self._fused_ok(dst, True):
+            if self._feeds_count_pass() and self._flat_ok(dst, dtype, True):
                 self._count_mean(dst, False, 0.0)
                 return dst
             c = self.count.to(dtype)
@@ -345,7 +347,7 @@ class AllReduceOutput:
             return dst
         if d.is_cuda:
             dst = torch.empty_like(d) if out is None else out
-            if self._fused_ok(dst):
+            if self._feeds_count_pass() and self._flat_ok(dst, d.dtype):
                 self._count_mean(dst, False, 0.0)
                 return dst
         c = self.count.to(d.dtype if d.is_floating_point() else torch.float32)

@@ -159,10 +159,7 @@ def dp_sgd_step(model: nn.Module, x: torch.Tensor, y: torch.Tensor, lr: float,
             bucket = GradientBucket(list(model.parameters()))
             model._akka_bucket = bucket  # type: ignore[attr-defined]
     loss = _forward_backward(model, x, y, bucket, compute_dtype, direct_grads, shadow_weights, fused_loss)
-    if optimizer is None:
-        bucket.sgd_from(allreduce, lr)
-    else:
-        optimizer.step_from(allreduce, lr)
+    bucket.update_from(allreduce, lr, optimizer or bucket.sgd)
     return float(loss.detach()) if sync_loss else loss.detach()
 
 
@@ -234,7 +231,7 @@ class GraphedDPStep:
             raise ValueError("GraphedDPStep: the optimizer was built on another bucket")
         if bucket.pflat is None or not bucket.bound() or not bucket.params_bound():
             raise ValueError("GraphedDPStep: needs GradientBucket(flatten_params=True) bound to the model")
-        self.model, self.bucket, self.optimizer = model, bucket, optimizer
+        self.model, self.bucket, self.rule = model, bucket, optimizer or bucket.sgd
         self.compute_dtype = compute_dtype
         self.lowp = compute_dtype if (shadow_weights and compute_dtype is not None
                                       and compute_dtype != torch.float32) else None
@@ -269,10 +266,8 @@ class GraphedDPStep:
         def fb():
             loss = _forward_backward(model, self.sx, self.sy, bucket, compute_dtype, True, shadow_weights, True,
                                      grad_seed=self._seed)
-            if self.allreduce is not None and optimizer is not None:
-                optimizer.step_from(self.allreduce, float(lr), out_buf=self._out)
-            elif self.allreduce is not None:
-                bucket.sgd_from(self.allreduce, float(lr), out_buf=self._out)
+            if self.allreduce is not None:
+                bucket.update_from(self.allreduce, float(lr), self.rule, out_buf=self._out)
             return loss
 
         # warm up and capture on ONE stream: the kernels' per-stream workspaces
@@ -280,14 +275,10 @@ class GraphedDPStep:
         # warmup, so the graph holds no fill for them
         side = torch.cuda.Stream(device=x.device)
         side.wait_stream(torch.cuda.current_stream(x.device))
-        # a captured update changes the parameters in the warmup steps: they
-        # are put back afterwards (the warmup's rounds still ran on every rank)
-        snap = bucket.pflat.clone() if self.allreduce is not None else None
-        # ... and so is a compressed bucket's error-feedback residual
-        rsnap = bucket.residual.clone() if (self.allreduce is not None and bucket.residual is not None) else None
-        # ... and the optimizer's state and step counter
-        osnap = [s.clone() for s in optimizer.state_tensors()] \
-            if (self.allreduce is not None and optimizer is not None) else None
+        # a captured update changes the parameters, a compressed bucket's residual and the rule's state in the
+        # warmup steps: they are put back afterwards (the warmup's rounds still ran on every rank)
+        snap = (bucket.snapshot(), [s.clone() for s in self.rule.state_tensors()]) \
+            if self.allreduce is not None else None
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 fb()
@@ -300,14 +291,8 @@ class GraphedDPStep:
             self.loss = fb().detach()
         torch.cuda.current_stream(x.device).wait_stream(side)
         if snap is not None:
-            bucket.pflat.copy_(snap)
-            if bucket.sflat is not None:
-                bucket.sflat.copy_(bucket.pflat)
-            bucket._shadow_versions = [p._version for p in bucket.params]
-        if rsnap is not None:
-            bucket.residual.copy_(rsnap)
-        if osnap is not None:
-            for s, keep in zip(optimizer.state_tensors(), osnap):
+            bucket.restore(snap[0])
+            for s, keep in zip(self.rule.state_tensors(), snap[1]):
                 s.copy_(keep)
         self._ptrs = self._pointers()  # the shadow exists now
 
@@ -317,11 +302,7 @@ class GraphedDPStep:
         return self.sx, self.sy
 
     def _pointers(self):
-        b = self.bucket
-        return (b.flat.data_ptr(), b.pflat.data_ptr(), b.sflat.data_ptr() if b.sflat is not None else 0,
-                [p.data_ptr() for p in b.params], [p.grad.data_ptr() if p.grad is not None else 0 for p in b.params],
-                b.wire.data_ptr() if b.wire is not None else 0, b.residual.data_ptr() if b.residual is not None else 0,
-                self.optimizer.state_pointers() if self.optimizer is not None else ())
+        return self.bucket.pointers(), self.rule.state_pointers()
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, lr: float, allreduce: Optional[AllreduceFn],
                  sync_loss: bool = False):
@@ -343,14 +324,10 @@ class GraphedDPStep:
             self.graph.replay()  # forward + backward + allreduce + fused update
             self.replays += 1
             self.allreduce.note_replays(1)
-            if b._shadow_on:
-                b._shadow_versions = [p._version for p in b.params]
+            b.shadow_written()
         else:
             self.graph.replay()
-            if self.optimizer is None:
-                b.sgd_from(allreduce, lr)
-            else:
-                self.optimizer.step_from(allreduce, lr)
+            b.update_from(allreduce, lr, self.rule)
         return float(self.loss) if sync_loss else self.loss
 
 

@@ -13,9 +13,7 @@ from typing import Optional, Sequence
 import torch
 
 from .._native_loader import load as _load
-from ..data import Geometry
-
-_DT = {torch.float32: "float32", torch.bfloat16: "bfloat16"}
+from ..data import DTYPE_NAME as _DT, Geometry, counts_table
 
 
 def _stream(t: torch.Tensor) -> int:
@@ -61,8 +59,7 @@ def count_expand(per_chunk: torch.Tensor, geometry: Geometry) -> torch.Tensor:
         raise ValueError("per_chunk must have workerNum * kmax entries")
     if per_chunk.device.type != "cuda":
         return geometry.expand_counts(per_chunk)
-    n = _load()
     out = torch.empty(geometry.dataSize, dtype=torch.int32, device=per_chunk.device)
-    n.count_expand(out.data_ptr(), per_chunk.data_ptr(), geometry.dataSize, geometry.step, geometry.workerNum,
-                   geometry.maxChunkSize, geometry.kmax, _stream(per_chunk))
+    pc, table = counts_table(per_chunk, geometry)
+    _load().count_expand(out.data_ptr(), table, _stream(per_chunk))
     return out

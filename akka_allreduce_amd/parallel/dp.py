@@ -15,7 +15,7 @@ from typing import Callable, List, Optional
 
 import torch
 
-from ..data import AllReduceOutput
+from ..data import AllReduceOutput, Geometry
 
 AllreduceFn = Callable[[torch.Tensor], AllReduceOutput]
 
@@ -59,6 +59,10 @@ class GradientBucket:
         self.sflat: Optional[torch.Tensor] = None
         self._shadow_on = False
         self._shadow_versions: Optional[List[int]] = None
+        self.sgd = PlainSGD()
+        # without an allreduce the bucket is a round of one contributor
+        self._solo = AllReduceOutput(self.flat, counts_per_chunk=torch.ones((1, 1), dtype=torch.int32, device=dev),
+                                     geometry=Geometry(self.numel, 1, self.numel))
         if flatten_params and all(p.dtype == dt for p in self.params):
             self.pflat = torch.empty(self.numel, dtype=dt, device=dev)
         off = 0
@@ -171,11 +175,7 @@ class GradientBucket:
         """flat <- mean over contributors (no-op without an allreduce)."""
         if allreduce is None:
             return None
-        if self.wire is not None:
-            out = self._wire_round(allreduce, None)
-            out.mean(out=self.flat, dtype=self.flat.dtype)
-            return out
-        out = allreduce(self.flat)
+        out = self._round(allreduce)
         self.average_out(out)  # one fused pass on the GPU, straight into the bucket
         return out
 
@@ -187,7 +187,10 @@ class GradientBucket:
         if self.residual is not None:
             self.residual.zero_()
 
-    def _wire_round(self, allreduce: AllreduceFn, out_buf: Optional[torch.Tensor]) -> AllReduceOutput:
+    def _round(self, allreduce: AllreduceFn, out_buf: Optional[torch.Tensor] = None) -> AllReduceOutput:
+        """One round over the gradients, packed onto the compressed ``wire`` when there is one."""
+        if self.wire is None:
+            return allreduce(self.flat) if out_buf is None else allreduce(self.flat, out=out_buf)
         from ..ops.compress import pack_bf16
 
         if out_buf is not None and out_buf.dtype != self.wire_dtype:
@@ -199,44 +202,78 @@ class GradientBucket:
                                "build the engine with dtype=torch.bfloat16")
         return out
 
+    def update_from(self, allreduce: Optional[AllreduceFn], lr: float, rule,
+                    out_buf: Optional[torch.Tensor] = None) -> Optional[AllReduceOutput]:
+        """Run the round and hand its output to ``rule`` (``self.sgd``, a ``FusedSGD`` or a ``FusedAdamW`` on this
+        bucket), which updates the parameters and the shadow it is given.  Without an allreduce, None is
+        returned: a rule that ``needs_round`` gets the bucket as a round of one contributor, any other gets
+        None and leaves the shadow to the next ``use_shadow``."""
+        out = self._solo if rule.needs_round else None
+        if allreduce is not None:
+            out = self._round(allreduce, out_buf)
+        rule.apply(self, out, lr, self.sflat if self._shadow_on else None)
+        if out is not None:
+            self.shadow_written()
+        return None if allreduce is None else out
+
+    def shadow_written(self) -> None:
+        """An update wrote the shadow with the parameters: it is current for their versions as they are now
+        (the kernels write through raw pointers and bump none; ``sgd_step``'s in-place adds bump them)."""
+        if self._shadow_on:
+            self._shadow_versions = [p._version for p in self.params]
+
     def sgd_from(self, allreduce: Optional[AllreduceFn], lr: float,
                  out_buf: Optional[torch.Tensor] = None) -> Optional[AllReduceOutput]:
         """Average the gradients over the contributors and apply SGD.  With
         flattened parameters this is one fused pass over the allreduce output
         (no averaged-gradient tensor is written).  ``out_buf``: the round's
         output buffer (reused; a captured step needs fixed buffers)."""
-        if allreduce is None:
-            sgd_step(self.params, lr)
-            return None
-        if self.wire is not None:
-            out = self._wire_round(allreduce, out_buf)
-            if self.pflat is not None:
-                # bf16 sum -> fp32 parameters (and the bf16 shadow): the same single pass
-                out.axpy_mean_(self.pflat, -lr, shadow=self.sflat if self._shadow_on else None, wide=True)
-            else:
-                out.mean(out=self.flat, dtype=self.flat.dtype)
-                sgd_step(self.params, lr)
-            if self._shadow_on:
-                self._shadow_versions = [p._version for p in self.params]
-            return out
-        out = allreduce(self.flat) if out_buf is None else allreduce(self.flat, out=out_buf)
-        if self.pflat is not None and out.data.dtype == self.pflat.dtype:
-            out.axpy_mean_(self.pflat, -lr, shadow=self.sflat if self._shadow_on else None)
-        else:
-            self.average_out(out)
-            sgd_step(self.params, lr)
-            if self._shadow_on and self.sflat is not None:
-                self.sflat.copy_(self.pflat)
-        if self._shadow_on:
-            # versions after our own update (sgd_step's in-place adds bump them)
-            self._shadow_versions = [p._version for p in self.params]
-        return out
+        return self.update_from(allreduce, lr, self.sgd, out_buf)
 
     def average_out(self, out: AllReduceOutput) -> None:
-        if out.data.dtype == self.flat.dtype:
-            out.mean(out=self.flat)
+        if out.data.dtype == self.flat.dtype or self.wire is not None:
+            out.mean(out=self.flat, dtype=self.flat.dtype)  # a compressed wire: the fp32 mean of its bf16 sum
         else:
             self.flat.copy_(out.mean().to(self.flat.dtype))
+
+    def snapshot(self) -> tuple:
+        """Copies of what an update changes, the flat parameters and the error-feedback residual, for ``restore``."""
+        return tuple(None if x is None else x.clone() for x in (self.pflat, self.residual))
+
+    def restore(self, snap: tuple) -> None:
+        for x, keep in zip((self.pflat, self.residual), snap):
+            if keep is not None:
+                x.copy_(keep)
+        if self.sflat is not None:
+            self.sflat.copy_(self.pflat)
+        self.shadow_written()
+
+    def pointers(self) -> tuple:
+        """Addresses of every buffer a captured step reads or writes."""
+        bufs = (self.flat, self.pflat, self.sflat, self.wire, self.residual)
+        return ([0 if x is None else x.data_ptr() for x in bufs],
+                [p.data_ptr() for p in self.params], [0 if p.grad is None else p.grad.data_ptr() for p in self.params])
+
+
+class PlainSGD:
+    """The plain SGD update as a rule of ``GradientBucket.update_from`` (``bucket.sgd``): ``p -= lr * mean``,
+    fused into the averaging where the parameters are flat."""
+
+    needs_round = False  # without an allreduce: the per-parameter update of the local gradients
+    state_tensors = state_pointers = staticmethod(lambda: ())  # no state
+
+    def apply(self, b: GradientBucket, out: Optional[AllReduceOutput], lr: float,
+              shadow: Optional[torch.Tensor]) -> None:
+        if out is None:
+            sgd_step(b.params, lr)
+        elif b.pflat is not None and (b.wire is not None or out.data.dtype == b.pflat.dtype):
+            # one pass into the parameters (and the bf16 shadow); a compressed wire's bf16 sum is read wide
+            out.axpy_mean_(b.pflat, -lr, shadow=shadow, wide=b.wire is not None)
+        else:
+            b.average_out(out)
+            sgd_step(b.params, lr)
+            if shadow is not None:
+                shadow.copy_(b.pflat)
 
 
 def sgd_step(params: List[torch.nn.Parameter], lr: float) -> None:

@@ -51,7 +51,7 @@ import torch
 
 from .._native_loader import load as _load
 from ..utils import tracing as _tracing
-from ..data import AllReduceOutput, Geometry
+from ..data import AllReduceOutput, Geometry, counts_table
 from ..worker import _raw_stream
 from .collective import _handle_exchange, env_rank_world
 
@@ -406,8 +406,8 @@ class OneSidedAllreduce:
     def _expand(self, per_chunk: torch.Tensor) -> torch.Tensor:
         g = self.geometry
         out = torch.empty(g.dataSize, dtype=torch.int32, device=per_chunk.device)
-        _load().count_expand(out.data_ptr(), per_chunk.contiguous().data_ptr(), g.dataSize, g.step, g.workerNum,
-                             g.maxChunkSize, g.kmax, torch.cuda.current_stream(per_chunk.device).cuda_stream)
+        pc, table = counts_table(per_chunk, g)
+        _load().count_expand(out.data_ptr(), table, torch.cuda.current_stream(per_chunk.device).cuda_stream)
         return out
 
     # ---- control / observability ------------------------------------------------

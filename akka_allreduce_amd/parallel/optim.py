@@ -28,12 +28,14 @@ from typing import Optional, Tuple
 
 import torch
 
-from ..data import AllReduceOutput, Geometry, sqnorm_workspace
+from ..data import AllReduceOutput, sqnorm_workspace
 from .dp import AllreduceFn, GradientBucket
 
 
 class _FusedOptimizer:
     kind = ""
+    hyper: Tuple[str, ...] = ()  # the attributes ``optim_step_`` takes as keywords
+    needs_round = True  # without an allreduce: the bucket's round of one contributor
 
     def __init__(self, bucket: GradientBucket, max_grad_norm: Optional[float]):
         if bucket.pflat is None or bucket.pflat.dtype != torch.float32 or bucket.flat.dtype != torch.float32:
@@ -49,17 +51,10 @@ class _FusedOptimizer:
         self.v: Optional[torch.Tensor] = None
         self.t = torch.zeros(1, dtype=torch.int32, device=dev)
         self.norm_ws = sqnorm_workspace(dev) if max_grad_norm is not None else None
-        # without an allreduce the bucket is a round of one contributor
-        self._solo_counts = torch.ones((1, 1), dtype=torch.int32, device=dev)
-        self._solo_geometry = Geometry(bucket.numel, 1, bucket.numel)
-
-    def _hyper(self) -> dict:
-        raise NotImplementedError
 
     def state_pointers(self) -> Tuple[int, ...]:
         """Addresses of everything a captured step reads or writes."""
-        return (self.m.data_ptr(), self.v.data_ptr() if self.v is not None else 0, self.t.data_ptr(),
-                self.norm_ws.data_ptr() if self.norm_ws is not None else 0)
+        return tuple(0 if x is None else x.data_ptr() for x in (self.m, self.v, self.t, self.norm_ws))
 
     def state_tensors(self) -> Tuple[torch.Tensor, ...]:
         return tuple(x for x in (self.m, self.v, self.t) if x is not None)
@@ -71,27 +66,20 @@ class _FusedOptimizer:
         this optimizer).  ``out_buf``: the round's output buffer (reused; a
         captured step needs fixed buffers).  ``allreduce=None``: this rank's
         gradients alone, as a round of one contributor."""
-        b = self.bucket
-        if allreduce is None:
-            out = AllReduceOutput(b.flat, counts_per_chunk=self._solo_counts, geometry=self._solo_geometry)
-        elif b.wire is not None:
-            out = b._wire_round(allreduce, out_buf)
-        else:
-            out = allreduce(b.flat) if out_buf is None else allreduce(b.flat, out=out_buf)
+        return self.bucket.update_from(allreduce, lr, self, out_buf)
+
+    def apply(self, bucket: GradientBucket, out: AllReduceOutput, lr: float, shadow: Optional[torch.Tensor]) -> None:
+        """The rule of ``GradientBucket.update_from``: one fused pass over the round's output."""
         self.t.add_(1)
-        out.optim_step_(self.kind, b.pflat, self.m, self.v, self.t, lr, shadow=b.sflat if b._shadow_on else None,
-                        max_norm=self.max_grad_norm, norm_ws=self.norm_ws, **self._hyper())
-        if b._shadow_on:
-            # our kernel writes through raw pointers: the shadow is current for these versions
-            b._shadow_versions = [p._version for p in b.params]
-        return None if allreduce is None else out
+        out.optim_step_(self.kind, bucket.pflat, self.m, self.v, self.t, lr, shadow=shadow, max_norm=self.max_grad_norm,
+                        norm_ws=self.norm_ws, **{k: getattr(self, k) for k in self.hyper})
 
 
 class FusedSGD(_FusedOptimizer):
     """``torch.optim.SGD(momentum, nesterov, weight_decay)`` (dampening 0) on a
     ``GradientBucket(flatten_params=True)``, fused into the averaging."""
 
-    kind = "sgd"
+    kind, hyper = "sgd", ("momentum", "nesterov", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, momentum: float = 0.9, nesterov: bool = False,
                  weight_decay: float = 0.0, max_grad_norm: Optional[float] = None):
@@ -102,15 +90,12 @@ class FusedSGD(_FusedOptimizer):
         super().__init__(bucket, max_grad_norm)
         self.momentum, self.nesterov, self.weight_decay = float(momentum), bool(nesterov), float(weight_decay)
 
-    def _hyper(self) -> dict:
-        return {"momentum": self.momentum, "nesterov": self.nesterov, "weight_decay": self.weight_decay}
-
 
 class FusedAdamW(_FusedOptimizer):
     """``torch.optim.AdamW(betas, eps, weight_decay)`` on a
     ``GradientBucket(flatten_params=True)``, fused into the averaging."""
 
-    kind = "adamw"
+    kind, hyper = "adamw", ("betas", "eps", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, max_grad_norm: Optional[float] = None):
@@ -119,6 +104,3 @@ class FusedAdamW(_FusedOptimizer):
         super().__init__(bucket, max_grad_norm)
         self.v = torch.zeros_like(bucket.pflat)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-
-    def _hyper(self) -> dict:
-        return {"betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay}

@@ -41,6 +41,19 @@ void bind_probe(py::module_& m);                    // bind_probe.cpp
 
 namespace {
 
+DType parse_dtype(const std::string& dtype) {
+  if (dtype == "float32" || dtype == "f32" || dtype == "fp32") return DType::F32;
+  if (dtype == "bfloat16" || dtype == "bf16") return DType::BF16;
+  throw AkkaError("akka: unsupported dtype " + dtype);
+}
+
+// A counts table as Python passes it: (counts pointer, S, step, N, C, kmax).
+using CountsArgs = std::tuple<uintptr_t, int64_t, int64_t, int32_t, int64_t, int32_t>;
+CountsTable counts_table(const CountsArgs& a) {
+  const auto [counts, S, step, N, C, kmax] = a;
+  return {reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax};
+}
+
 struct PySimHub {
   std::shared_ptr<SimHub> hub;
 };
@@ -83,10 +96,8 @@ class OutboxLink final : public Link {
 class WorkerCore final : public EngineHost {
  public:
   WorkerCore(py::object host, std::string link, int32_t device, std::string dtype, bool deferred, int32_t lag)
-      : host_(std::move(host)), link_kind_(std::move(link)), device_idx_(device), deferred_(deferred), lag_(lag) {
-    if (dtype == "float32" || dtype == "f32" || dtype == "fp32") dt_ = DType::F32;
-    else if (dtype == "bfloat16" || dtype == "bf16") dt_ = DType::BF16;
-    else throw AkkaError("akka: unsupported dtype " + dtype);
+      : host_(std::move(host)), link_kind_(std::move(link)), device_idx_(device), deferred_(deferred), lag_(lag),
+        dt_(parse_dtype(dtype)) {
     AKKA_CHECK(link_kind_ == "outbox" || link_kind_ == "stream" || link_kind_ == "reactive",
                "link must be 'outbox', 'stream' or 'reactive'");
     engine_ = std::make_unique<Engine>(this, nullptr);
@@ -408,18 +419,11 @@ class WorkerCore final : public EngineHost {
     dev_->sync_stream(dev_->compute_stream());
     dev_->sync_stream(dev_->comm_stream());
   }
-  void count_mean(uintptr_t dst, uintptr_t src, uintptr_t counts, uintptr_t stream) {
-    const Geometry& g = engine_->geometry();
-    AKKA_CHECK(dev_ && !dev_->is_host(), "count_mean: device path only");
-    launch_count_mean(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<void*>(dst),
-                      reinterpret_cast<const void*>(src), reinterpret_cast<const int32_t*>(counts), g.S, g.step, g.N,
-                      g.C, dp_->kmax(), dt_, dt_);
-  }
   void expand_counts(uintptr_t out, uintptr_t counts, uintptr_t stream) {
     const Geometry& g = engine_->geometry();
     AKKA_CHECK(dev_ && !dev_->is_host(), "expand_counts: device path only");
     launch_count_expand(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<int32_t*>(out),
-                        reinterpret_cast<const int32_t*>(counts), g.S, g.step, g.N, g.C, dp_->kmax());
+                        counts_table({counts, g.S, g.step, g.N, g.C, dp_->kmax()}));
   }
 
   std::pair<uintptr_t, uintptr_t> streams() const {
@@ -888,7 +892,6 @@ PYBIND11_MODULE(_native, m) {
       .def("exec_on_producer", &WorkerCore::exec_on_producer)
       .def("sync_all", &WorkerCore::sync_all)
       .def("expand_counts", &WorkerCore::expand_counts)
-      .def("count_mean", &WorkerCore::count_mean)
       .def("drain", &WorkerCore::drain)
       .def("drain_frames", &WorkerCore::drain_frames)
       .def("apply_frame", &WorkerCore::apply_frame)
@@ -1055,7 +1058,7 @@ PYBIND11_MODULE(_native, m) {
   // ---- kernels (tests / microbench) ----------------------------------------------
   m.def("reduce", [](uintptr_t dst, std::vector<uintptr_t> srcs, int64_t n, std::string dtype, uintptr_t stream,
                      std::string impl) {
-    DType dt = (dtype == "bfloat16" || dtype == "bf16") ? DType::BF16 : DType::F32;
+    const DType dt = parse_dtype(dtype);
     ReduceImpl im = reduce_impl_from_name(impl.c_str());
     std::vector<const void*> ptrs;
     for (auto p : srcs) ptrs.push_back(reinterpret_cast<const void*>(p));
@@ -1063,59 +1066,42 @@ PYBIND11_MODULE(_native, m) {
     for (const auto& spec : split_reduce(reinterpret_cast<void*>(dst), ptrs, n)) launch_reduce(as_stream(stream), spec, dt, im);
   }, py::arg("dst"), py::arg("srcs"), py::arg("n"), py::arg("dtype") = "float32", py::arg("stream") = 0,
         py::arg("impl") = "auto");
-  m.def("count_expand", [](uintptr_t out, uintptr_t counts, int64_t S, int64_t step, int32_t N, int64_t C,
-                           int32_t kmax, uintptr_t stream) {
-    launch_count_expand(as_stream(stream), reinterpret_cast<int32_t*>(out), reinterpret_cast<const int32_t*>(counts),
-                        S, step, N, C, kmax);
+  m.def("count_expand", [](uintptr_t out, const CountsArgs& table, uintptr_t stream) {
+    launch_count_expand(as_stream(stream), reinterpret_cast<int32_t*>(out), counts_table(table));
   });
-  m.def("count_mean", [](uintptr_t dst, uintptr_t src, uintptr_t counts, int64_t S, int64_t step, int32_t N,
-                         int64_t C, int32_t kmax, std::string dtype, uintptr_t stream, bool axpy, float alpha,
-                         uintptr_t shadow, std::string src_dtype) {
-    const DType dt = dtype == "bfloat16" ? DType::BF16 : DType::F32;
+  m.def("count_mean", [](uintptr_t dst, uintptr_t src, const CountsArgs& table, const std::string& dtype,
+                         uintptr_t stream, bool axpy, float alpha, uintptr_t shadow, const std::string& src_dtype) {
+    const DType dt = parse_dtype(dtype);
     // src_dtype "": the source has the destination's dtype
-    const DType sdt = src_dtype.empty() ? dt : (src_dtype == "bfloat16" ? DType::BF16 : DType::F32);
     launch_count_mean(as_stream(stream), reinterpret_cast<void*>(dst), reinterpret_cast<const void*>(src),
-                      reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax, dt, sdt, axpy, alpha,
+                      counts_table(table), dt, src_dtype.empty() ? dt : parse_dtype(src_dtype), axpy, alpha,
                       reinterpret_cast<void*>(shadow));
-  }, py::arg("dst"), py::arg("src"), py::arg("counts"), py::arg("S"), py::arg("step"), py::arg("N"), py::arg("C"),
-     py::arg("kmax"), py::arg("dtype"), py::arg("stream"), py::arg("axpy") = false, py::arg("alpha") = 0.f,
-     py::arg("shadow") = 0, py::arg("src_dtype") = "");
-  m.def("count_optim", [](std::string kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow, uintptr_t src,
-                          std::string src_dtype, uintptr_t counts, int64_t S, int64_t step, int32_t N, int64_t C,
-                          int32_t kmax, uintptr_t t, uintptr_t sq, double lr, double weight_decay, double momentum,
-                          bool nesterov, double beta1, double beta2, double eps, double max_norm, uintptr_t stream,
-                          bool nt) {
+  }, py::arg("dst"), py::arg("src"), py::arg("table"), py::arg("dtype"), py::arg("stream"), py::arg("axpy") = false,
+     py::arg("alpha") = 0.f, py::arg("shadow") = 0, py::arg("src_dtype") = "");
+  // the hyper-parameters are keyword-only: OptimSpec's fields, with its defaults
+  m.def("count_optim", [](const std::string& kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow,
+                          uintptr_t src, const std::string& src_dtype, const CountsArgs& table, uintptr_t t,
+                          uintptr_t sq, uintptr_t stream, bool nt, double lr, double weight_decay, double momentum,
+                          bool nesterov, double beta1, double beta2, double eps, double max_norm) {
     AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim: kind is 'sgd' or 'adamw'");
-    AKKA_CHECK(src_dtype == "float32" || src_dtype == "bfloat16", "count_optim: the sum is float32 or bfloat16");
-    OptimSpec o;
-    o.kind = kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD;
-    o.lr = lr;
-    o.weight_decay = weight_decay;
-    o.momentum = momentum;
-    o.nesterov = nesterov;
-    o.beta1 = beta1;
-    o.beta2 = beta2;
-    o.eps = eps;
-    o.max_norm = max_norm;
+    const OptimSpec o{kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD, lr, weight_decay, momentum, nesterov,
+                      beta1, beta2, eps, max_norm};
     launch_count_optim(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<float*>(mom),
                        reinterpret_cast<float*>(v), reinterpret_cast<void*>(shadow),
-                       reinterpret_cast<const void*>(src), src_dtype == "bfloat16" ? DType::BF16 : DType::F32,
-                       reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax, o,
+                       reinterpret_cast<const void*>(src), parse_dtype(src_dtype), counts_table(table), o,
                        reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), nt);
   }, py::arg("kind"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("src"),
-     py::arg("src_dtype"), py::arg("counts"), py::arg("S"), py::arg("step"), py::arg("N"), py::arg("C"),
-     py::arg("kmax"), py::arg("t"), py::arg("sq"), py::arg("lr"), py::arg("weight_decay") = 0.0,
-     py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
-     py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0, py::arg("stream") = 0, py::arg("nt") = false);
-  m.def("count_sqnorm", [](uintptr_t sq, uintptr_t src, std::string src_dtype, uintptr_t counts, int64_t S,
-                           int64_t step, int32_t N, int64_t C, int32_t kmax, uintptr_t part, uintptr_t ticket,
-                           uintptr_t stream) {
-    AKKA_CHECK(src_dtype == "float32" || src_dtype == "bfloat16", "count_sqnorm: the sum is float32 or bfloat16");
+     py::arg("src_dtype"), py::arg("table"), py::arg("t"), py::arg("sq"), py::arg("stream") = 0,
+     py::arg("nt") = false, py::kw_only(), py::arg("lr"), py::arg("weight_decay") = 0.0, py::arg("momentum") = 0.0,
+     py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-8,
+     py::arg("max_norm") = 0.0);
+  m.def("count_sqnorm", [](uintptr_t sq, uintptr_t src, const std::string& src_dtype, const CountsArgs& table,
+                           uintptr_t part, uintptr_t ticket, uintptr_t stream) {
     launch_count_sqnorm(as_stream(stream), reinterpret_cast<float*>(sq), reinterpret_cast<const void*>(src),
-                        src_dtype == "bfloat16" ? DType::BF16 : DType::F32, reinterpret_cast<const int32_t*>(counts),
-                        S, step, N, C, kmax, reinterpret_cast<float*>(part), reinterpret_cast<uint32_t*>(ticket));
-  }, py::arg("sq"), py::arg("src"), py::arg("src_dtype"), py::arg("counts"), py::arg("S"), py::arg("step"),
-     py::arg("N"), py::arg("C"), py::arg("kmax"), py::arg("part"), py::arg("ticket"), py::arg("stream") = 0);
+                        parse_dtype(src_dtype), counts_table(table), reinterpret_cast<float*>(part),
+                        reinterpret_cast<uint32_t*>(ticket));
+  }, py::arg("sq"), py::arg("src"), py::arg("src_dtype"), py::arg("table"), py::arg("part"), py::arg("ticket"),
+     py::arg("stream") = 0);
   m.def("count_sqnorm_partials", &count_sqnorm_partials);
   m.def("pack_bf16", [](uintptr_t dst, uintptr_t src, uintptr_t residual, int64_t n, uintptr_t stream) {
     AKKA_CHECK(n >= 0 && (n == 0 || (dst != 0 && src != 0)), "pack_bf16: null buffer");

@@ -199,20 +199,21 @@ void launch_poison_counts(hipStream_t s, const uint32_t* flag, int32_t* counts, 
                      flag, counts, n);
 }
 
-void launch_count_expand(hipStream_t s, int32_t* out, const int32_t* counts, int64_t S, int64_t step, int32_t N,
-                         int64_t C, int32_t kmax) {
-  if (S <= 0) return;
+void launch_count_expand(hipStream_t s, int32_t* out, const CountsTable& t) {
+  if (t.S <= 0) return;
+  t.check("count_expand");
   // out must be 16-B aligned for the vector stores (torch allocations are)
   AKKA_CHECK((reinterpret_cast<uintptr_t>(out) & 15) == 0, "count_expand: output not 16-B aligned");
-  const auto [grid, split] = region_grid(int64_t(N) * kmax, S, kMaxGrid);
-  hipLaunchKernelGGL(count_expand_kernel, dim3(grid, split), dim3(kBlock), 0, s, out, counts, S, step, N, C, kmax);
+  const auto [grid, split] = region_grid(t.regions(), t.S, kMaxGrid);
+  hipLaunchKernelGGL(count_expand_kernel, dim3(grid, split), dim3(kBlock), 0, s, out, t.counts, t.S, t.step, t.N, t.C,
+                     t.kmax);
   check_launch("count_expand");
 }
 
-void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t* counts, int64_t S, int64_t step,
-                       int32_t N, int64_t C, int32_t kmax, DType dt, DType src_dt, bool axpy, float alpha,
-                       void* shadow) {
-  if (S <= 0) return;
+void launch_count_mean(hipStream_t s, void* dst, const void* src, const CountsTable& t, DType dt, DType src_dt,
+                       bool axpy, float alpha, void* shadow) {
+  if (t.S <= 0) return;
+  t.check("count_mean");
   AKKA_CHECK(src_dt == dt || (dt == DType::F32 && src_dt == DType::BF16),
              "count_mean: the source is the destination's dtype, or bf16 into fp32");
   AKKA_CHECK((reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0,
@@ -224,11 +225,11 @@ void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t*
     const char* v = std::getenv("AKKA_CM_MAXGRID");
     return v && std::atoll(v) > 0 ? int64_t(std::atoll(v)) : int64_t(kMaxGrid);
   }();
-  const auto [grid, split] = region_grid(int64_t(N) * kmax, S, max_grid);
-#define AKKA_CM(TD, TS, AX, SH)                                                                             \
-  hipLaunchKernelGGL((count_mean_kernel<TD, TS, AX, SH>), dim3(grid, split), dim3(kBlock), 0, s,             \
-                     static_cast<TD*>(dst), static_cast<const TS*>(src), counts, S, step, N, C, kmax, alpha, \
-                     static_cast<bf16_t*>(shadow))
+  const auto [grid, split] = region_grid(t.regions(), t.S, max_grid);
+#define AKKA_CM(TD, TS, AX, SH)                                                                               \
+  hipLaunchKernelGGL((count_mean_kernel<TD, TS, AX, SH>), dim3(grid, split), dim3(kBlock), 0, s,               \
+                     static_cast<TD*>(dst), static_cast<const TS*>(src), t.counts, t.S, t.step, t.N, t.C, t.kmax, \
+                     alpha, static_cast<bf16_t*>(shadow))
   if (dt == DType::F32 && src_dt == DType::BF16) {
     if (shadow) AKKA_CM(float, bf16_t, true, true);
     else if (axpy) AKKA_CM(float, bf16_t, true, false);

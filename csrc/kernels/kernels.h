@@ -21,16 +21,26 @@ ReduceImpl reduce_impl_from_name(const char* name);
 
 // dst = sum(srcs) over n elements (fp32 accumulate).
 void launch_reduce(hipStream_t s, const ReduceSpec& spec, DType dt, ReduceImpl impl);
-// counts[N][kmax] (per block, per chunk) -> out[S] (per element), RB:41-47.
-void launch_count_expand(hipStream_t s, int32_t* out, const int32_t* counts, int64_t S, int64_t step, int32_t N,
-                         int64_t C, int32_t kmax);
+// A round's contributor counts[N][kmax] (per block, per chunk) and their layout: what every count pass walks.
+struct CountsTable {
+  const int32_t* counts;
+  int64_t S, step;
+  int32_t N;
+  int64_t C;
+  int32_t kmax;
+  int64_t regions() const { return int64_t(N) * kmax; }
+  void check(const char* who) const {
+    AKKA_CHECK(regions() > 0 && step >= 0 && C > 0, std::string(who) + ": bad geometry");
+  }
+};
+// counts -> out[S] (per element), RB:41-47.
+void launch_count_expand(hipStream_t s, int32_t* out, const CountsTable& t);
 // dst = src / per-chunk count (0 where the count is 0), one pass; with
 // `axpy`: dst += alpha * that mean (fused SGD update).  dt is the
 // destination's dtype, src_dt the source's: the same, or bf16 into fp32 (the
 // sum of a compressed wire read straight into fp32 gradients / parameters).
-void launch_count_mean(hipStream_t s, void* dst, const void* src, const int32_t* counts, int64_t S, int64_t step,
-                       int32_t N, int64_t C, int32_t kmax, DType dt, DType src_dt, bool axpy = false,
-                       float alpha = 0.f, void* shadow = nullptr);
+void launch_count_mean(hipStream_t s, void* dst, const void* src, const CountsTable& t, DType dt, DType src_dt,
+                       bool axpy = false, float alpha = 0.f, void* shadow = nullptr);
 // The fused optimizer step over a round's output (optim.hip).  Per element
 // g = src / per-chunk count, times min(1, max_norm / (sqrt(*sq) + 1e-6)) when
 // `sq` is given, then torch.optim.SGD's update (momentum, dampening 0) or
@@ -49,13 +59,12 @@ struct OptimSpec {
   double max_norm = 0;                            // used with sq
 };
 void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
-                        const int32_t* counts, int64_t S, int64_t step, int32_t N, int64_t C, int32_t kmax,
-                        const OptimSpec& o, const int32_t* t, const float* sq, bool nt = false);
+                        const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq, bool nt = false);
 // sq[0] = sum over the elements whose count is > 0 of (src / count)^2.  part:
 // fp32 [count_sqnorm_partials()] workspace; ticket: one uint32 zeroed once
 // (each launch leaves it zero again).  Deterministic for a given shape.
-void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const int32_t* counts, int64_t S,
-                         int64_t step, int32_t N, int64_t C, int32_t kmax, float* part, uint32_t* ticket);
+void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const CountsTable& ct, float* part,
+                         uint32_t* ticket);
 int32_t count_sqnorm_partials();
 // q (bf16) = rne(g + r), r = (g + r) - float(q) in place; r may be null (a
 // plain cast).  r becomes 0 where the sum or its rounding is not finite.

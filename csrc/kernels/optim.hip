@@ -310,14 +310,13 @@ bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 
 }  // namespace
 
 void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
-                        const int32_t* counts, int64_t S, int64_t step, int32_t N, int64_t C, int32_t kmax,
-                        const OptimSpec& o, const int32_t* t, const float* sq, bool nt) {
-  if (S <= 0) return;
+                        const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq, bool nt) {
+  if (ct.S <= 0) return;
   const bool adam = o.kind == OptimKind::AdamW;
-  AKKA_CHECK(p && m && src && counts && (!adam || (v && t)), "count_optim: null buffer");
+  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)), "count_optim: null buffer");
   AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
              "count_optim: buffers must be 16-B aligned");
-  AKKA_CHECK(int64_t(N) * kmax > 0 && step >= 0 && C > 0, "count_optim: bad geometry");
+  ct.check("count_optim");
   OptimK k{};
   k.neg_lr = float(-o.lr);
   k.wd = float(o.weight_decay);
@@ -331,11 +330,11 @@ void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shado
   k.w2 = float(1.0 - o.beta2);
   k.eps = float(o.eps);
   k.max_norm = float(o.max_norm);
-  const auto [grid, split] = region_grid(int64_t(N) * kmax, S, kMaxGrid);
+  const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
   auto* h = static_cast<bf16_t*>(shadow);
 #define AKKA_OPT(TS, AD, SH, NTV)                                                                              \
   hipLaunchKernelGGL((count_optim_kernel<TS, AD, SH, NTV>), dim3(grid, split), dim3(kBlock), 0, s, p, m, v, h, \
-                     static_cast<const TS*>(src), counts, S, step, N, C, kmax, k, t, sq)
+                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, t, sq)
 #define AKKA_OPT_NT(TS, AD, SH)       \
   do {                                \
     if (nt) AKKA_OPT(TS, AD, SH, true); \
@@ -361,18 +360,18 @@ void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shado
 
 int32_t count_sqnorm_partials() { return kMaxGrid; }
 
-void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const int32_t* counts, int64_t S,
-                         int64_t step, int32_t N, int64_t C, int32_t kmax, float* part, uint32_t* ticket) {
-  if (S <= 0) return;
-  AKKA_CHECK(sq && src && counts && part && ticket, "count_sqnorm: null buffer");
+void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const CountsTable& ct, float* part,
+                         uint32_t* ticket) {
+  if (ct.S <= 0) return;
+  AKKA_CHECK(sq && src && ct.counts && part && ticket, "count_sqnorm: null buffer");
   AKKA_CHECK(aligned16(src), "count_sqnorm: the sum must be 16-B aligned");
-  AKKA_CHECK(int64_t(N) * kmax > 0 && step >= 0 && C > 0, "count_sqnorm: bad geometry");
+  ct.check("count_sqnorm");
   // grid * split <= kMaxGrid: one partial each in `part`
-  const auto [grid, split] = region_grid(int64_t(N) * kmax, S, kMaxGrid);
+  const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
   // plain loads: the update pass reads the sum next
 #define AKKA_SQ(TS)                                                                                          \
   hipLaunchKernelGGL((count_sqnorm_kernel<TS>), dim3(grid, split), dim3(kBlock), 0, s, sq,                   \
-                     static_cast<const TS*>(src), counts, S, step, N, C, kmax, part, ticket)
+                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, part, ticket)
   if (src_dt == DType::BF16) AKKA_SQ(bf16_t);
   else AKKA_SQ(float);
 #undef AKKA_SQ

@@ -89,6 +89,65 @@ def sqnorm_workspace(device) -> torch.Tensor:
     return torch.zeros(2 + n, dtype=torch.float32, device=device)
 
 
+class OptimGroups:
+    """Parameter groups of ``AllReduceOutput.optim_step_(groups=...)``: the
+    flat buffer cut into segments and one row of scalars per group, all in
+    device memory so the update reads them when it RUNS (a captured step
+    follows whatever the rows hold at each replay).
+
+    ``seg_end``: ascending exclusive ends of the segments (the last one is the
+    buffer's size); ``seg_group``: each segment's group.  ``rows`` is float32
+    ``[groups, 4]`` = ``{-lr_g, wd_g, lr_g, 1 - lr_g * wd_g}``, each computed
+    in double and rounded once (``row_values``); ``write_rows`` uploads them
+    with one stream-ordered copy on the current stream."""
+
+    __slots__ = ("seg_end", "seg_group", "rows", "host_seg_end", "host_seg_group", "ngroups", "numel")
+
+    def __init__(self, seg_end, seg_group, ngroups: int, device):
+        self.host_seg_end = [int(e) for e in seg_end]
+        self.host_seg_group = [int(g) for g in seg_group]
+        self.ngroups = int(ngroups)
+        prev = 0
+        for e, g in zip(self.host_seg_end, self.host_seg_group):
+            if e <= prev:
+                raise ValueError(f"OptimGroups: segment ends must be positive and ascending, got {self.host_seg_end}")
+            if not 0 <= g < self.ngroups:
+                raise ValueError(f"OptimGroups: group {g} is outside [0, {self.ngroups})")
+            prev = e
+        if not self.host_seg_end or len(self.host_seg_end) != len(self.host_seg_group):
+            raise ValueError("OptimGroups: one group per segment, at least one segment")
+        self.numel = prev
+        device = torch.device(device)
+        self.seg_end = torch.tensor(self.host_seg_end, dtype=torch.int64, device=device)
+        self.seg_group = torch.tensor(self.host_seg_group, dtype=torch.int32, device=device)
+        self.rows = torch.zeros((self.ngroups, 4), dtype=torch.float32, device=device)  # allocated once
+
+    @staticmethod
+    def row_values(lr: float, group_hyper) -> torch.Tensor:
+        """The rows of ``[(lr_scale, weight_decay)]`` at learning rate ``lr``, as a CPU tensor."""
+        rows = []
+        for scale, wd in group_hyper:
+            lr_g = float(lr) * float(scale)
+            rows.append([-lr_g, float(wd), lr_g, 1.0 - lr_g * float(wd)])
+        return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+    def write_rows(self, values: torch.Tensor) -> None:
+        if values.shape != self.rows.shape or values.dtype != torch.float32:
+            raise ValueError(f"OptimGroups: rows are float32 {tuple(self.rows.shape)}")
+        if self.rows.is_cuda:
+            # pinned staging from torch's caching host allocator: the copy is ordered on the current stream and
+            # the block is not reused before it ran
+            self.rows.copy_(values.pin_memory(), non_blocking=True)
+        else:
+            self.rows.copy_(values)
+
+    def expand(self, column: int) -> torch.Tensor:
+        """One column of the rows as a per-element vector (the torch path of ``optim_step_``)."""
+        ends = torch.tensor(self.host_seg_end, dtype=torch.int64, device=self.rows.device)
+        lens = torch.diff(ends, prepend=ends.new_zeros(1))
+        return torch.repeat_interleave(self.rows[:, column][self.seg_group.long()], lens)
+
+
 @dataclass
 class AllReduceInputRequest:
     iteration: int
@@ -207,7 +266,7 @@ class AllReduceOutput:
                     lr: float, *, weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
                     betas: tuple = (0.9, 0.999), eps: float = 1e-8, shadow: Optional[torch.Tensor] = None,
                     max_norm: Optional[float] = None, norm_ws: Optional[torch.Tensor] = None,
-                    nt: bool = False) -> torch.Tensor:
+                    nt: bool = False, groups: Optional[OptimGroups] = None) -> torch.Tensor:
         """One optimizer step of the flat fp32 parameters ``p`` from this
         round, in one fused pass on the GPU: per element ``g = sum / count``,
         then ``kind="sgd"`` (``torch.optim.SGD``: weight decay into ``g``,
@@ -233,7 +292,14 @@ class AllReduceOutput:
         ``axpy_mean_``'s fused pass (anything else raises); CPU tensors run the
         same formulas as torch operations.  ``nt`` streams with nontemporal
         accesses instead of plain ones (slower where measured: kept for
-        ``bench/fused_opt.py``).  Returns ``p``."""
+        ``bench/fused_opt.py``).
+
+        ``groups`` (``OptimGroups``) gives every segment of the buffer its
+        group's learning rate and weight decay, read from the groups' device
+        rows when the pass runs: ``lr`` and ``weight_decay`` are then not used
+        (nor ``nt``).  A group whose learning rate is 0 advances ``m`` / ``v``
+        and leaves ``p`` where it is (times its decay of 1); the shadow is
+        still written.  Returns ``p``."""
         self.wait()
         if kind not in ("sgd", "adamw"):
             raise ValueError(f"optim_step_: kind={kind!r} (sgd or adamw)")
@@ -251,6 +317,9 @@ class AllReduceOutput:
             raise ValueError("optim_step_: t is one int32 on p's device")
         if max_norm is not None and norm_ws is None:
             raise ValueError("optim_step_: max_norm needs a norm workspace (sqnorm_workspace)")
+        if groups is not None and (groups.numel != d.numel() or groups.rows.device != d.device):
+            raise ValueError(f"optim_step_: the groups cover {groups.numel} elements on {groups.rows.device}, the "
+                             f"round has {d.numel()} on {d.device}")
         if d.is_cuda:
             if not (self._feeds_count_pass() and all(self._flat_ok(s, torch.float32) for _, s in [("p", p)] + state)
                     and (shadow is None or self._flat_ok(shadow, torch.bfloat16))):
@@ -260,6 +329,17 @@ class AllReduceOutput:
 
             sq = self.sqnorm(norm_ws) if max_norm is not None else None
             pc, table = counts_table(self.counts_per_chunk, self.geometry)
+            if groups is not None:
+                load().count_optim_groups(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
+                                          shadow.data_ptr() if shadow is not None else 0, d.data_ptr(),
+                                          DTYPE_NAME[d.dtype], table, t.data_ptr(),
+                                          sq.data_ptr() if sq is not None else 0, groups.seg_end.data_ptr(),
+                                          groups.seg_group.data_ptr(), groups.rows.data_ptr(), groups.host_seg_end,
+                                          groups.host_seg_group, groups.ngroups,
+                                          torch.cuda.current_stream(d.device).cuda_stream, momentum=momentum,
+                                          nesterov=nesterov, beta1=betas[0], beta2=betas[1], eps=eps,
+                                          max_norm=max_norm if max_norm is not None else 0.0)
+                return p
             load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
                                shadow.data_ptr() if shadow is not None else 0, d.data_ptr(), DTYPE_NAME[d.dtype],
                                table, t.data_ptr(), sq.data_ptr() if sq is not None else 0,
@@ -274,7 +354,24 @@ class AllReduceOutput:
         if max_norm is not None:
             sq = self.sqnorm(norm_ws)
             g = g * torch.clamp(max_norm / (sq.sqrt() + 1e-6), max=1.0)
-        if adam:
+        if groups is not None:
+            # the formulas below with per-element vectors expanded from the rows in place of the scalars
+            neg_lr, wd, lr_v, decay = (groups.expand(c).view_as(p) for c in range(4))
+            moves = lr_v != 0  # lr 0: the state advances, p only takes its decay (AdamW's step is 0 / -0 at v = 0)
+            if adam:
+                b1, b2 = betas
+                tf = t.to(torch.float32)
+                pd = p * decay
+                mn = torch.lerp(m, g, 1 - b1)
+                vn = (v * b2).addcmul_(g, g, value=1 - b2)
+                nss = -(lr_v / (1 - b1 ** tf))
+                pn = torch.where(moves, pd.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(eps / nss)), pd)
+                v.copy_(torch.where(keep, v, vn))
+            else:
+                g = torch.addcmul(g, p, wd)
+                mn = (m * momentum).add_(g)
+                pn = torch.where(moves, torch.addcmul(p, g.add(mn, alpha=momentum) if nesterov else mn, neg_lr), p)
+        elif adam:
             b1, b2 = betas
             tf = t.to(torch.float32)
             pn = p * (1 - lr * weight_decay)

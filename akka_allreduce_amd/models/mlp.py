@@ -212,7 +212,10 @@ class GraphedDPStep:
     step: forward, backward, allreduce and update in one replay.  ``optimizer=``
     (``parallel.FusedSGD`` / ``FusedAdamW`` on this bucket) puts its fused pass
     where the plain SGD update is, captured or not; its step counter lives on
-    the device, so a captured update advances it on every replay.  The ~30 launches of
+    the device, so a captured update advances it on every replay; one built with
+    ``param_groups`` / ``device_lr`` keeps its learning rate there too, so a
+    captured step may be called with another ``lr`` every time (any other rule
+    keeps the one it was captured with, and a different one raises).  The ~30 launches of
     the forward/backward cost one replay instead of ~10 µs of host time each
     (the step is otherwise host-bound at this size).
 
@@ -294,6 +297,8 @@ class GraphedDPStep:
             bucket.restore(snap[0])
             for s, keep in zip(self.rule.state_tensors(), snap[1]):
                 s.copy_(keep)
+            if self._device_lr():
+                self.rule.set_lr(float(lr))  # the rows are no state to restore: they hold the captured lr
         self._ptrs = self._pointers()  # the shadow exists now
 
     def static_inputs(self):
@@ -303,6 +308,9 @@ class GraphedDPStep:
 
     def _pointers(self):
         return self.bucket.pointers(), self.rule.state_pointers()
+
+    def _device_lr(self) -> bool:
+        return bool(getattr(self.rule, "device_lr", False))
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, lr: float, allreduce: Optional[AllreduceFn],
                  sync_loss: bool = False):
@@ -319,7 +327,12 @@ class GraphedDPStep:
         if self.allreduce is not None:
             if allreduce is not None and allreduce is not self.allreduce:
                 raise RuntimeError("GraphedDPStep: the step captured another allreduce")
-            if lr != self.lr:
+            if self._device_lr():
+                # the update reads its learning rate from device memory: written before the replay
+                if lr != self.rule.lr:
+                    self.rule.set_lr(lr)
+                self.lr = lr
+            elif lr != self.lr:
                 raise RuntimeError(f"GraphedDPStep: the update was captured with lr={self.lr}")
             self.graph.replay()  # forward + backward + allreduce + fused update
             self.replays += 1

@@ -78,6 +78,14 @@ class GradientBucket:
     def zero_(self) -> None:
         self.flat.zero_()
 
+    def spans(self) -> List[tuple]:
+        """``(offset, numel)`` of every parameter in the flat buffers, in the bucket's order."""
+        out, off = [], 0
+        for p in self.params:
+            out.append((off, p.numel()))
+            off += p.numel()
+        return out
+
     # ---- bf16 shadow weights -------------------------------------------------
     # A bf16 forward under autocast casts every fp32 weight to bf16 each step
     # (4 B read + 2 B written per parameter).  With flattened fp32 parameters

@@ -18,18 +18,27 @@ so a parameter does not drift on stale momentum because a round dropped its
 chunk.  AdamW's bias corrections use the global step for every element.
 
 The step counter ``t`` lives on the device (one int32, advanced by an in-place
-add before the pass), so a captured step advances it on every replay.  The
+add before the pass), so a captured step advances it on every replay.
+
+Built plainly, an optimizer has one weight decay for the whole buffer and its
 learning rate is a launch argument: a captured step keeps the one it was
-captured with.
+captured with.  ``param_groups=`` (per-group ``weight_decay`` and ``lr_scale``)
+or ``device_lr=True`` move both into a small device table, one row per group,
+that the pass reads when it runs (``data.OptimGroups``): biases and norm
+scales can stay out of the decay, and ``set_lr`` between two replays of a
+captured step changes its learning rate.  Betas, eps, momentum and the clip
+norm stay per optimizer.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from ..data import AllReduceOutput, sqnorm_workspace
+from ..data import AllReduceOutput, OptimGroups, sqnorm_workspace
 from .dp import AllreduceFn, GradientBucket
+
+_GROUP_KEYS = ("params", "weight_decay", "lr_scale")
 
 
 class _FusedOptimizer:
@@ -51,13 +60,173 @@ class _FusedOptimizer:
         self.v: Optional[torch.Tensor] = None
         self.t = torch.zeros(1, dtype=torch.int32, device=dev)
         self.norm_ws = sqnorm_workspace(dev) if max_grad_norm is not None else None
+        self.device_lr = False
+        self.groups: Optional[OptimGroups] = None  # segments and the device rows (device_lr)
+        self._group_hyper: List[Dict[str, Any]] = []
+        self._lr: Optional[float] = None  # the learning rate the rows hold
+
+    # ---- parameter groups ------------------------------------------------------
+
+    def _init_groups(self, param_groups, device_lr: bool) -> None:
+        """Called by the subclass once ``weight_decay`` is set."""
+        b = self.bucket
+        spans = b.spans()
+        if param_groups is None:
+            if device_lr:
+                param_groups = []
+            else:
+                self._group_hyper = [{"lr_scale": 1.0, "weight_decay": self.weight_decay, "spans": [(0, b.numel)]}]
+                return
+        index = {id(p): i for i, p in enumerate(b.params)}
+        owner: List[Optional[int]] = [None] * len(b.params)
+        hyper = []
+        for gi, g in enumerate(param_groups):
+            if not isinstance(g, dict) or "params" not in g:
+                raise ValueError(f"param_groups[{gi}]: a dict with 'params'")
+            unknown = sorted(set(g) - set(_GROUP_KEYS))
+            if unknown:
+                raise ValueError(f"param_groups[{gi}]: unknown key {unknown[0]!r} (known: {', '.join(_GROUP_KEYS)})")
+            wd, scale = float(g.get("weight_decay", self.weight_decay)), float(g.get("lr_scale", 1.0))
+            if not (wd >= 0 and scale >= 0):
+                raise ValueError(f"param_groups[{gi}]: weight_decay and lr_scale are >= 0")
+            ps = g["params"]
+            ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            if not ps:
+                raise ValueError(f"param_groups[{gi}]: no parameters")
+            for p in ps:
+                i = index.get(id(p))
+                if i is None:
+                    raise ValueError(f"param_groups[{gi}]: a parameter that is not in the bucket")
+                if owner[i] is not None:
+                    raise ValueError(f"param_groups[{gi}]: parameter {i} of the bucket is already in group {owner[i]}")
+                owner[i] = gi
+            hyper.append({"lr_scale": scale, "weight_decay": wd, "spans": []})
+        if any(o is None for o in owner):  # listed nowhere: a last group with the defaults
+            hyper.append({"lr_scale": 1.0, "weight_decay": self.weight_decay, "spans": []})
+            owner = [len(hyper) - 1 if o is None else o for o in owner]
+        # adjacent parameters of one group are one segment
+        seg_end: List[int] = []
+        seg_group: List[int] = []
+        for (off, n), gi in zip(spans, owner):
+            if n == 0:
+                continue
+            if seg_group and seg_group[-1] == gi:
+                seg_end[-1] = off + n
+                o, k = hyper[gi]["spans"][-1]
+                hyper[gi]["spans"][-1] = (o, k + n)
+            else:
+                seg_end.append(off + n)
+                seg_group.append(gi)
+                hyper[gi]["spans"].append((off, n))
+        self.device_lr = True
+        self._group_hyper = hyper
+        self.groups = OptimGroups(seg_end, seg_group, len(hyper), b.pflat.device)
+
+    @property
+    def param_groups(self) -> List[Dict[str, Any]]:
+        """Copies of the groups: ``lr_scale``, ``weight_decay`` and the ``spans`` (offset, numel) of the flat
+        buffer each one covers.  Change them with ``set_group``."""
+        return [{"lr_scale": g["lr_scale"], "weight_decay": g["weight_decay"], "spans": list(g["spans"])}
+                for g in self._group_hyper]
+
+    @property
+    def lr(self) -> Optional[float]:
+        """The learning rate the device rows hold (None: none uploaded yet, or no ``device_lr``)."""
+        return self._lr
+
+    def _need_device_lr(self, what: str) -> None:
+        if not self.device_lr:
+            raise RuntimeError(f"{type(self).__name__}.{what}: built without param_groups / device_lr, the learning "
+                               "rate and the weight decay are launch arguments")
+
+    def _upload(self) -> None:
+        self.groups.write_rows(OptimGroups.row_values(
+            self._lr, [(g["lr_scale"], g["weight_decay"]) for g in self._group_hyper]))
+
+    def set_lr(self, lr: float) -> None:
+        """Recompute the groups' rows for ``lr`` on the host and upload them (one stream-ordered copy on the
+        current stream): the next pass, eager or replayed, steps with it."""
+        self._need_device_lr("set_lr")
+        self._lr = float(lr)
+        self._upload()
+
+    def set_group(self, i: int, weight_decay: Optional[float] = None, lr_scale: Optional[float] = None) -> None:
+        self._need_device_lr("set_group")
+        g = self._group_hyper[i]
+        for key, val in (("weight_decay", weight_decay), ("lr_scale", lr_scale)):
+            if val is not None:
+                if not float(val) >= 0:
+                    raise ValueError(f"set_group: {key} is >= 0")
+                g[key] = float(val)
+        if self._lr is not None:
+            self._upload()
+
+    # ---- state -------------------------------------------------------------------
 
     def state_pointers(self) -> Tuple[int, ...]:
         """Addresses of everything a captured step reads or writes."""
-        return tuple(0 if x is None else x.data_ptr() for x in (self.m, self.v, self.t, self.norm_ws))
+        gr = self.groups
+        return tuple(0 if x is None else x.data_ptr() for x in (
+            self.m, self.v, self.t, self.norm_ws, *((gr.rows, gr.seg_end, gr.seg_group) if gr is not None else ())))
 
     def state_tensors(self) -> Tuple[torch.Tensor, ...]:
         return tuple(x for x in (self.m, self.v, self.t) if x is not None)
+
+    def _hyper_dict(self) -> Dict[str, Any]:
+        return {**{k: getattr(self, k) for k in self.hyper}, "max_grad_norm": self.max_grad_norm}
+
+    def state_dict(self) -> Dict[str, Any]:
+        """The optimizer's state with cloned tensors (``t`` is read from the device: a host sync)."""
+        return {"kind": self.kind, "numel": self.bucket.numel, "t": int(self.t), "m": self.m.clone(),
+                "v": None if self.v is None else self.v.clone(), "hyper": self._hyper_dict(), "lr": self._lr,
+                "param_groups": self.param_groups}
+
+    def load_state_dict(self, d: Dict[str, Any]) -> None:
+        """Load a ``state_dict`` of an optimizer of the same kind, size and group layout.  Everything is copied
+        IN PLACE: no address changes, so a captured step stays valid.  The hyper-parameters that are launch
+        arguments (betas, eps, momentum, the clip norm; without ``device_lr`` the weight decay too) must match
+        the ones this optimizer was built with -- a captured step has them baked in; the groups' weight decay
+        and lr scale and the uploaded learning rate are taken from ``d`` and the rows written again."""
+        if d.get("kind") != self.kind:
+            raise ValueError(f"load_state_dict: kind {d.get('kind')!r}, this optimizer is {self.kind!r}")
+        if d.get("numel") != self.bucket.numel:
+            raise ValueError(f"load_state_dict: numel {d.get('numel')}, this bucket has {self.bucket.numel}")
+        mine, theirs = self._group_hyper, list(d.get("param_groups") or [])
+        if len(mine) != len(theirs):
+            raise ValueError(f"load_state_dict: {len(theirs)} param_groups, this optimizer has {len(mine)}")
+        for i, (a, b) in enumerate(zip(mine, theirs)):
+            if [tuple(s) for s in b["spans"]] != [tuple(s) for s in a["spans"]]:
+                raise ValueError(f"load_state_dict: param_groups[{i}] spans {list(b['spans'])}, this optimizer "
+                                 f"has {a['spans']}")
+        hyper = d.get("hyper") or {}
+        for k, mine_v in self._hyper_dict().items():
+            if k == "weight_decay" and self.device_lr:
+                continue  # per group, in the rows
+            theirs_v = hyper.get(k)
+            theirs_v = tuple(theirs_v) if isinstance(theirs_v, (list, tuple)) else theirs_v
+            if theirs_v != mine_v:
+                raise ValueError(f"load_state_dict: {k}={theirs_v!r}, this optimizer was built with {mine_v!r} "
+                                 "(a launch argument)")
+        if not self.device_lr and (theirs[0]["lr_scale"] != 1.0 or theirs[0]["weight_decay"] != self.weight_decay):
+            raise ValueError("load_state_dict: the group's lr_scale / weight_decay differ; without device_lr they "
+                             "are launch arguments")
+        if (d.get("v") is None) != (self.v is None):
+            raise ValueError("load_state_dict: v does not match the optimizer's kind")
+        for name, dst in (("m", self.m), ("v", self.v)):
+            if dst is not None and (d[name].shape != dst.shape or d[name].dtype != dst.dtype):
+                raise ValueError(f"load_state_dict: {name} is {d[name].dtype} {tuple(d[name].shape)}")
+        self.m.copy_(d["m"])
+        if self.v is not None:
+            self.v.copy_(d["v"])
+        self.t.fill_(int(d["t"]))
+        if self.device_lr:
+            for a, b in zip(mine, theirs):
+                a["lr_scale"], a["weight_decay"] = float(b["lr_scale"]), float(b["weight_decay"])
+            self._lr = None if d.get("lr") is None else float(d["lr"])
+            if self._lr is not None:
+                self._upload()
+
+    # ---- the step ------------------------------------------------------------------
 
     def step_from(self, allreduce: Optional[AllreduceFn], lr: float,
                   out_buf: Optional[torch.Tensor] = None) -> Optional[AllReduceOutput]:
@@ -70,37 +239,55 @@ class _FusedOptimizer:
 
     def apply(self, bucket: GradientBucket, out: AllReduceOutput, lr: float, shadow: Optional[torch.Tensor]) -> None:
         """The rule of ``GradientBucket.update_from``: one fused pass over the round's output."""
+        if self.device_lr and lr != self._lr:
+            # the rows are written outside a graph: a capture holds the pass, never the upload
+            if self.t.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}: lr={lr} while capturing, the rows hold {self._lr}; call "
+                                   "set_lr before the capture")
+            self.set_lr(lr)
         self.t.add_(1)
         out.optim_step_(self.kind, bucket.pflat, self.m, self.v, self.t, lr, shadow=shadow, max_norm=self.max_grad_norm,
-                        norm_ws=self.norm_ws, **{k: getattr(self, k) for k in self.hyper})
+                        norm_ws=self.norm_ws, groups=self.groups, **{k: getattr(self, k) for k in self.hyper})
 
 
 class FusedSGD(_FusedOptimizer):
     """``torch.optim.SGD(momentum, nesterov, weight_decay)`` (dampening 0) on a
-    ``GradientBucket(flatten_params=True)``, fused into the averaging."""
+    ``GradientBucket(flatten_params=True)``, fused into the averaging.
+
+    ``param_groups``: a list of dicts ``{"params": [...], "weight_decay": wd,
+    "lr_scale": s}`` (both optional: the optimizer's ``weight_decay`` and 1.0)
+    over parameters of the bucket, each in at most one group; the parameters
+    listed nowhere form a last group with the defaults.  A group steps with
+    ``lr * lr_scale``.  ``device_lr=True`` alone is one group; either keeps the
+    learning rate in device memory (``set_lr``)."""
 
     kind, hyper = "sgd", ("momentum", "nesterov", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, momentum: float = 0.9, nesterov: bool = False,
-                 weight_decay: float = 0.0, max_grad_norm: Optional[float] = None):
+                 weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, param_groups=None,
+                 device_lr: bool = False):
         if momentum < 0 or weight_decay < 0:
             raise ValueError("FusedSGD: momentum and weight_decay are >= 0")
         if nesterov and momentum <= 0:
             raise ValueError("FusedSGD: Nesterov momentum needs momentum > 0")
         super().__init__(bucket, max_grad_norm)
         self.momentum, self.nesterov, self.weight_decay = float(momentum), bool(nesterov), float(weight_decay)
+        self._init_groups(param_groups, device_lr)
 
 
 class FusedAdamW(_FusedOptimizer):
     """``torch.optim.AdamW(betas, eps, weight_decay)`` on a
-    ``GradientBucket(flatten_params=True)``, fused into the averaging."""
+    ``GradientBucket(flatten_params=True)``, fused into the averaging.
+    ``param_groups`` / ``device_lr`` as for ``FusedSGD``."""
 
     kind, hyper = "adamw", ("betas", "eps", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.01, max_grad_norm: Optional[float] = None):
+                 weight_decay: float = 0.01, max_grad_norm: Optional[float] = None, param_groups=None,
+                 device_lr: bool = False):
         if not (0 <= betas[0] < 1 and 0 <= betas[1] < 1) or eps < 0 or weight_decay < 0:
             raise ValueError("FusedAdamW: betas in [0, 1), eps and weight_decay >= 0")
         super().__init__(bucket, max_grad_norm)
         self.v = torch.zeros_like(bucket.pflat)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self._init_groups(param_groups, device_lr)

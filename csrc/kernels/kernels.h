@@ -60,6 +60,27 @@ struct OptimSpec {
 };
 void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
                         const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq, bool nt = false);
+// The same step with parameter groups and a device-resident learning rate.
+// The flat buffer is cut into `nseg` segments: seg_end (device, int64) holds
+// their ascending exclusive ends, the last one S, seg_group (device, int32)
+// each segment's group in [0, ngroups); host_seg_end / host_seg_group are the
+// host copies the launcher checks.  rows (device, float[ngroups][4], 16-B
+// aligned) = {float(-lr_g), float(wd_g), float(lr_g), float(1 - lr_g * wd_g)}
+// per group, read when the kernel RUNS: rewriting them between the replays of a
+// captured step changes its schedule.  o.lr and o.weight_decay are not used;
+// momentum, nesterov, betas, eps and max_norm stay launch arguments.  A group
+// whose lr is 0 advances m and v and leaves p (times its decay of 1) in place.
+struct OptimGroups {
+  const int64_t* seg_end = nullptr;
+  const int32_t* seg_group = nullptr;
+  const float* rows = nullptr;
+  int32_t nseg = 0, ngroups = 0;
+  const int64_t* host_seg_end = nullptr;
+  const int32_t* host_seg_group = nullptr;
+};
+void launch_count_optim_groups(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src,
+                               DType src_dt, const CountsTable& ct, const OptimSpec& o, const OptimGroups& g,
+                               const int32_t* t, const float* sq);
 // sq[0] = sum over the elements whose count is > 0 of (src / count)^2.  part:
 // fp32 [count_sqnorm_partials()] workspace; ticket: one uint32 zeroed once
 // (each launch leaves it zero again).  Deterministic for a given shape.

@@ -37,6 +37,11 @@
 // size; `nt` is kept so that bench/fused_opt.py can repeat the comparison
 // (table in profiles/r08/fused_opt/README.md).
 //
+// count_optim_groups: the same pass with per-group weight decay and learning
+// rate, both read from a small device table when the kernel runs (below, at
+// the kernel).  Both kernels share update_range / update_one and the
+// coefficient code; numbers in profiles/r09/param_groups/README.md.
+//
 // count_sqnorm: sq[0] = sum over count > 0 of (sum / count)^2, the squared
 // global norm of the mean gradient the clip needs.  fp32 partials per thread,
 // a fixed wave + workgroup tree, one partial per workgroup written through
@@ -67,29 +72,51 @@ struct OptimK {
 struct Coef {
   float clip;    // gradient scale
   float d1, d2;  // AdamW: p += m / (sqrt(v) / d1 + d2)
+  bool move;     // count_optim_groups: false for a group whose learning rate is 0
+};
+
+// The part of them that does not depend on the learning rate: once per kernel.
+struct StepCoef {
+  float clip;
+  float inv_bc1, sbc2;  // AdamW: 1 / (1 - b1^t), sqrt(1 - b2^t)
 };
 
 template <bool ADAM>
-__device__ __forceinline__ Coef coefficients(const OptimK& k, const int32_t* t, const float* sq) {
+__device__ __forceinline__ StepCoef step_coefficients(const OptimK& k, const int32_t* t, const float* sq) {
 #pragma clang fp contract(off)
-  Coef c{1.f, 0.f, 0.f};
+  StepCoef c{1.f, 0.f, 0.f};
   // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)), the quotient as reciprocal * max_norm
   if (sq) c.clip = fminf(1.f, (1.f / (sqrtf(*sq) + 1e-6f)) * k.max_norm);
   if constexpr (ADAM) {
-    // AdamW(capturable=True): bc_k = 1 - b_k^t in fp32; the step size lr / bc1
-    // and sqrt(bc2) folded into the denominator, eps scaled to match:
-    // p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+    // AdamW(capturable=True): bc_k = 1 - b_k^t in fp32
     const float tf = float(*t);
-    const float nss = -((1.f / (1.f - powf(k.b1, tf))) * k.lr);
-    c.d1 = sqrtf(1.f - powf(k.b2, tf)) * nss;
-    c.d2 = (1.f / nss) * k.eps;
+    c.inv_bc1 = 1.f / (1.f - powf(k.b1, tf));
+    c.sbc2 = sqrtf(1.f - powf(k.b2, tf));
+  }
+  return c;
+}
+
+// The part that does: once per kernel (count_optim) or per group sub-range (count_optim_groups).
+template <bool ADAM>
+__device__ __forceinline__ Coef lr_coefficients(const StepCoef& sc, float lr, float eps) {
+#pragma clang fp contract(off)
+  Coef c{sc.clip, 0.f, 0.f, lr != 0.f};
+  if constexpr (ADAM) {
+    // the step size lr / bc1 and sqrt(bc2) folded into the denominator, eps scaled to match:
+    // p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+    const float nss = -(sc.inv_bc1 * lr);
+    c.d1 = sc.sbc2 * nss;
+    c.d2 = (1.f / nss) * eps;
   }
   return c;
 }
 
 // One element.  No contraction but the fused multiply-adds spelled out: they
-// are the ones torch's add(alpha) / lerp / addcmul kernels make.
-template <bool ADAM>
+// are the ones torch's add(alpha) / lerp / addcmul kernels make.  GROUPS: a
+// group whose learning rate is 0 (a schedule's first step; c.move is false,
+// wave-uniform) advances the state, gives p its decay (a factor of 1) and no
+// step -- the step's formula is 0 / -0 there while v is 0.
+template <bool ADAM, bool GROUPS = false>
 __device__ __forceinline__ void update_one(float g, float& p, float& m, float& v, const OptimK& k, const Coef& c) {
 #pragma clang fp contract(off)
   g = g * c.clip;
@@ -98,13 +125,105 @@ __device__ __forceinline__ void update_one(float g, float& p, float& m, float& v
     const float d = g - m;  // m = b1 * m + (1 - b1) * g as lerp_ spells it
     m = k.w1 < 0.5f ? __builtin_fmaf(k.w1, d, m) : __builtin_fmaf(-d, 1.f - k.w1, g);
     v = __builtin_fmaf(k.w2, g * g, v * k.b2);
-    p = p + m / (sqrtf(v) / c.d1 + c.d2);
+    if (!GROUPS || c.move) p = p + m / (sqrtf(v) / c.d1 + c.d2);
   } else {
     g = __builtin_fmaf(k.wd, p, g);
     m = m * k.mu + g;
-    if (k.nesterov) g = __builtin_fmaf(k.mu, m, g);
-    else g = m;
-    p = __builtin_fmaf(k.neg_lr, g, p);
+    if (!GROUPS || c.move) {
+      if (k.nesterov) g = __builtin_fmaf(k.mu, m, g);
+      else g = m;
+      p = __builtin_fmaf(k.neg_lr, g, p);
+    }
+  }
+}
+
+// The elements [s, e) of one count region (fv: its count) with one set of
+// scalars: scalar head and tail outside the 8-aligned body, units in between,
+// split over the gridDim.y workgroups that share the region.
+template <typename TS, bool ADAM, bool SHADOW, bool NT, bool GROUPS = false>
+__device__ __forceinline__ void update_range(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                             bf16_t* __restrict__ shadow, const TS* __restrict__ src, int64_t s,
+                                             int64_t e, float fv, const OptimK& k, const Coef& c) {
+  constexpr int E = 8;                        // elements per unit
+  constexpr int ES = Elt<TS>::kPerVec;        // elements per source vector
+  constexpr int NS = E / ES;                  // source vectors per unit
+  constexpr int NF = E / Elt<float>::kPerVec; // fp32 vectors per unit and stream
+  int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first element 16-B aligned in every stream
+  if (a > e) a = e;
+  const int64_t nv = (e - a) / E;
+  auto one = [&](int64_t i) {
+    float pi = p[i], mi = m[i], vi = ADAM ? v[i] : 0.f;
+    update_one<ADAM, GROUPS>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
+    p[i] = pi;
+    m[i] = mi;
+    if constexpr (ADAM) v[i] = vi;
+    if constexpr (SHADOW) shadow[i] = Elt<bf16_t>::from_f(pi);
+  };
+  if (blockIdx.y == 0) {
+    for (int64_t i = s + threadIdx.x; i < a; i += kBlock) one(i);
+    for (int64_t i = a + nv * E + threadIdx.x; i < e; i += kBlock) one(i);
+  }
+  const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
+  v4u* p4 = reinterpret_cast<v4u*>(p + a);
+  v4u* m4 = reinterpret_cast<v4u*>(m + a);
+  v4u* v4 = reinterpret_cast<v4u*>(v + a);
+  v4u* h4 = reinterpret_cast<v4u*>(shadow + a);
+  auto ld = [](const v4u* q) { return NT ? __builtin_nontemporal_load(q) : *q; };
+  auto st = [](const v4u& x, v4u* q) {
+    if constexpr (NT) __builtin_nontemporal_store(x, q);
+    else *q = x;
+  };
+  struct Unit {
+    v4u s[NS], p[NF], m[NF], v[NF];
+  };
+  auto load = [&](int64_t at) {
+    Unit u;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) u.s[q] = ld(s4 + at * NS + q);
+#pragma unroll
+    for (int q = 0; q < NF; ++q) u.p[q] = ld(p4 + at * NF + q);
+#pragma unroll
+    for (int q = 0; q < NF; ++q) u.m[q] = ld(m4 + at * NF + q);
+    if constexpr (ADAM) {
+#pragma unroll
+      for (int q = 0; q < NF; ++q) u.v[q] = ld(v4 + at * NF + q);
+    }
+    return u;
+  };
+  auto update = [&](Unit& u, int64_t at) {
+    float g[E], pn[E];
+#pragma unroll
+    for (int q = 0; q < E; ++q) g[q] = 0.f;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) Elt<TS>::add(reinterpret_cast<float(&)[ES]>(g[q * ES]), u.s[q]);
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+      float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = __uint_as_float(u.m[q >> 2][q & 3]);
+      float vi = ADAM ? __uint_as_float(u.v[q >> 2][q & 3]) : 0.f;
+      update_one<ADAM, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
+      pn[q] = pi;
+      u.p[q >> 2][q & 3] = __float_as_uint(pi);
+      u.m[q >> 2][q & 3] = __float_as_uint(mi);
+      if constexpr (ADAM) u.v[q >> 2][q & 3] = __float_as_uint(vi);
+    }
+#pragma unroll
+    for (int q = 0; q < NF; ++q) {
+      st(u.p[q], p4 + at * NF + q);
+      st(u.m[q], m4 + at * NF + q);
+      if constexpr (ADAM) st(u.v[q], v4 + at * NF + q);
+    }
+    if constexpr (SHADOW) st(Elt<bf16_t>::pack(pn), h4 + at);
+  };
+  const int64_t stride = int64_t(kBlock) * gridDim.y;
+  int64_t i = int64_t(blockIdx.y) * kBlock + threadIdx.x;
+  for (; i + stride < nv; i += 2 * stride) {
+    Unit u0 = load(i), u1 = load(i + stride);
+    update(u0, i);
+    update(u1, i + stride);
+  }
+  for (; i < nv; i += stride) {
+    Unit u = load(i);
+    update(u, i);
   }
 }
 
@@ -116,11 +235,38 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
                                                              int64_t step, int32_t N, int64_t C, int32_t kmax,
                                                              OptimK k, const int32_t* __restrict__ t,
                                                              const float* __restrict__ sq) {
-  constexpr int E = 8;                        // elements per unit
-  constexpr int ES = Elt<TS>::kPerVec;        // elements per source vector
-  constexpr int NS = E / ES;                  // source vectors per unit
-  constexpr int NF = E / Elt<float>::kPerVec; // fp32 vectors per unit and stream
-  const Coef c = coefficients<ADAM>(k, t, sq);
+  const Coef c = lr_coefficients<ADAM>(step_coefficients<ADAM>(k, t, sq), k.lr, k.eps);
+  const int64_t nregions = int64_t(N) * kmax;
+  for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
+    const int32_t j = int32_t(reg / kmax);
+    const int64_t kk = reg - int64_t(j) * kmax;
+    const int64_t bs = j * step < S ? j * step : S;
+    const int64_t be = j >= N - 1 ? S : ((j + 1) * step < S ? (j + 1) * step : S);
+    const int64_t s = bs + kk * C;
+    if (s >= be) continue;
+    const int64_t e = s + C < be ? s + C : be;
+    const int32_t cnt = counts[reg];
+    if (cnt <= 0) continue;  // missing: nothing of this region is loaded or stored
+    update_range<TS, ADAM, SHADOW, NT>(p, m, v, shadow, src, s, e, float(cnt), k, c);
+  }
+}
+
+// count_optim with parameter groups.  The flat buffer is cut into segments
+// (seg_end: ascending exclusive ends, the last one S; seg_group: each
+// segment's group) and rows[g] = {neg_lr, wd, lr, decay} holds group g's
+// host-rounded scalars in DEVICE memory, read when the kernel runs: rewriting
+// the rows between the replays of a captured step changes its learning rate.
+// A region is walked by its intersections with the segments, each processed as
+// count_optim processes a region, with its group's row.  Everything that picks
+// the segment and the row is wave-uniform (scalar loads, scalar branches).
+template <typename TS, bool ADAM, bool SHADOW>
+__global__ __launch_bounds__(kBlock) void count_optim_groups_kernel(
+    float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ shadow,
+    const TS* __restrict__ src, const int32_t* __restrict__ counts, int64_t S, int64_t step, int32_t N, int64_t C,
+    int32_t kmax, OptimK k, const int32_t* __restrict__ t, const float* __restrict__ sq,
+    const int64_t* __restrict__ seg_end, const int32_t* __restrict__ seg_group, const float4* __restrict__ rows,
+    int32_t nseg, int32_t G) {
+  const StepCoef sc = step_coefficients<ADAM>(k, t, sq);
   const int64_t nregions = int64_t(N) * kmax;
   for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
     const int32_t j = int32_t(reg / kmax);
@@ -133,82 +279,30 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
     const int32_t cnt = counts[reg];
     if (cnt <= 0) continue;  // missing: nothing of this region is loaded or stored
     const float fv = float(cnt);
-    int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first element 16-B aligned in every stream
-    if (a > e) a = e;
-    const int64_t nv = (e - a) / E;
-    auto one = [&](int64_t i) {
-      float pi = p[i], mi = m[i], vi = ADAM ? v[i] : 0.f;
-      update_one<ADAM>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
-      p[i] = pi;
-      m[i] = mi;
-      if constexpr (ADAM) v[i] = vi;
-      if constexpr (SHADOW) shadow[i] = Elt<bf16_t>::from_f(pi);
-    };
-    if (blockIdx.y == 0) {
-      for (int64_t i = s + threadIdx.x; i < a; i += kBlock) one(i);
-      for (int64_t i = a + nv * E + threadIdx.x; i < e; i += kBlock) one(i);
+    // the first segment whose end is past s (there is one: the last segment ends at S > s)
+    int32_t lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+      const int32_t mid = (lo + hi) >> 1;
+      if (seg_end[mid] > s) hi = mid;
+      else lo = mid + 1;
     }
-    const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
-    v4u* p4 = reinterpret_cast<v4u*>(p + a);
-    v4u* m4 = reinterpret_cast<v4u*>(m + a);
-    v4u* v4 = reinterpret_cast<v4u*>(v + a);
-    v4u* h4 = reinterpret_cast<v4u*>(shadow + a);
-    auto ld = [](const v4u* q) { return NT ? __builtin_nontemporal_load(q) : *q; };
-    auto st = [](const v4u& x, v4u* q) {
-      if constexpr (NT) __builtin_nontemporal_store(x, q);
-      else *q = x;
-    };
-    struct Unit {
-      v4u s[NS], p[NF], m[NF], v[NF];
-    };
-    auto load = [&](int64_t at) {
-      Unit u;
-#pragma unroll
-      for (int q = 0; q < NS; ++q) u.s[q] = ld(s4 + at * NS + q);
-#pragma unroll
-      for (int q = 0; q < NF; ++q) u.p[q] = ld(p4 + at * NF + q);
-#pragma unroll
-      for (int q = 0; q < NF; ++q) u.m[q] = ld(m4 + at * NF + q);
-      if constexpr (ADAM) {
-#pragma unroll
-        for (int q = 0; q < NF; ++q) u.v[q] = ld(v4 + at * NF + q);
+    int64_t cur = s;
+    for (int32_t si = lo; cur < e && si < nseg; ++si) {
+      const int64_t se = seg_end[si];
+      const int64_t ee = se < e ? se : e;
+      if (ee <= cur) continue;
+      const uint32_t g = uint32_t(seg_group[si]);
+      if (g < uint32_t(G)) {  // the launcher checked the host copy; a row is never read out of bounds
+        const float4 r = rows[g];
+        OptimK kg = k;
+        kg.neg_lr = r.x;
+        kg.wd = r.y;
+        kg.lr = r.z;
+        kg.decay = r.w;
+        update_range<TS, ADAM, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
+                                                    lr_coefficients<ADAM>(sc, r.z, k.eps));
       }
-      return u;
-    };
-    auto update = [&](Unit& u, int64_t at) {
-      float g[E], pn[E];
-#pragma unroll
-      for (int q = 0; q < E; ++q) g[q] = 0.f;
-#pragma unroll
-      for (int q = 0; q < NS; ++q) Elt<TS>::add(reinterpret_cast<float(&)[ES]>(g[q * ES]), u.s[q]);
-#pragma unroll
-      for (int q = 0; q < E; ++q) {
-        float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = __uint_as_float(u.m[q >> 2][q & 3]);
-        float vi = ADAM ? __uint_as_float(u.v[q >> 2][q & 3]) : 0.f;
-        update_one<ADAM>(g[q] / fv, pi, mi, vi, k, c);
-        pn[q] = pi;
-        u.p[q >> 2][q & 3] = __float_as_uint(pi);
-        u.m[q >> 2][q & 3] = __float_as_uint(mi);
-        if constexpr (ADAM) u.v[q >> 2][q & 3] = __float_as_uint(vi);
-      }
-#pragma unroll
-      for (int q = 0; q < NF; ++q) {
-        st(u.p[q], p4 + at * NF + q);
-        st(u.m[q], m4 + at * NF + q);
-        if constexpr (ADAM) st(u.v[q], v4 + at * NF + q);
-      }
-      if constexpr (SHADOW) st(Elt<bf16_t>::pack(pn), h4 + at);
-    };
-    const int64_t stride = int64_t(kBlock) * gridDim.y;
-    int64_t i = int64_t(blockIdx.y) * kBlock + threadIdx.x;
-    for (; i + stride < nv; i += 2 * stride) {
-      Unit u0 = load(i), u1 = load(i + stride);
-      update(u0, i);
-      update(u1, i + stride);
-    }
-    for (; i < nv; i += stride) {
-      Unit u = load(i);
-      update(u, i);
+      cur = ee;
     }
   }
 }
@@ -356,6 +450,62 @@ void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shado
 #undef AKKA_OPT_NT
 #undef AKKA_OPT
   check_launch("count_optim");
+}
+
+void launch_count_optim_groups(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src,
+                               DType src_dt, const CountsTable& ct, const OptimSpec& o, const OptimGroups& g,
+                               const int32_t* t, const float* sq) {
+  if (ct.S <= 0) return;
+  const bool adam = o.kind == OptimKind::AdamW;
+  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)), "count_optim_groups: null buffer");
+  AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
+             "count_optim_groups: buffers must be 16-B aligned");
+  ct.check("count_optim_groups");
+  AKKA_CHECK(g.nseg > 0 && g.ngroups > 0 && g.seg_end && g.seg_group && g.rows && g.host_seg_end && g.host_seg_group,
+             "count_optim_groups: no segments, no groups or a null table");
+  AKKA_CHECK(aligned16(g.rows) && (reinterpret_cast<uintptr_t>(g.seg_end) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(g.seg_group) & 3) == 0,
+             "count_optim_groups: the rows must be 16-B aligned, the segment tables naturally");
+  int64_t prev = 0;
+  for (int32_t i = 0; i < g.nseg; ++i) {
+    AKKA_CHECK(g.host_seg_end[i] > prev, "count_optim_groups: segment ends must be positive and ascending");
+    AKKA_CHECK(g.host_seg_group[i] >= 0 && g.host_seg_group[i] < g.ngroups,
+               "count_optim_groups: a segment's group is outside [0, groups)");
+    prev = g.host_seg_end[i];
+  }
+  AKKA_CHECK(prev == ct.S, "count_optim_groups: the last segment must end at the buffer's size");
+  // the learning rate and the decay come from the rows; everything else is per optimizer
+  OptimK k{};
+  k.mu = float(o.momentum);
+  k.nesterov = o.nesterov ? 1 : 0;
+  k.b1 = float(o.beta1);
+  k.w1 = float(1.0 - o.beta1);
+  k.b2 = float(o.beta2);
+  k.w2 = float(1.0 - o.beta2);
+  k.eps = float(o.eps);
+  k.max_norm = float(o.max_norm);
+  const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
+  auto* h = static_cast<bf16_t*>(shadow);
+  const auto* rows = reinterpret_cast<const float4*>(g.rows);
+#define AKKA_OPTG(TS, AD, SH)                                                                                    \
+  hipLaunchKernelGGL((count_optim_groups_kernel<TS, AD, SH>), dim3(grid, split), dim3(kBlock), 0, s, p, m, v, h, \
+                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, t, sq,       \
+                     g.seg_end, g.seg_group, rows, g.nseg, g.ngroups)
+#define AKKA_OPTG_SH(TS, AD)            \
+  do {                                  \
+    if (shadow) AKKA_OPTG(TS, AD, true); \
+    else AKKA_OPTG(TS, AD, false);      \
+  } while (0)
+  if (src_dt == DType::BF16) {
+    if (adam) AKKA_OPTG_SH(bf16_t, true);
+    else AKKA_OPTG_SH(bf16_t, false);
+  } else {
+    if (adam) AKKA_OPTG_SH(float, true);
+    else AKKA_OPTG_SH(float, false);
+  }
+#undef AKKA_OPTG_SH
+#undef AKKA_OPTG
+  check_launch("count_optim_groups");
 }
 
 int32_t count_sqnorm_partials() { return kMaxGrid; }

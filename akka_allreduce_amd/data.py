@@ -89,6 +89,40 @@ def sqnorm_workspace(device) -> torch.Tensor:
     return torch.zeros(2 + n, dtype=torch.float32, device=device)
 
 
+def _mul32(x: torch.Tensor, c: int) -> torch.Tensor:
+    """``x * c`` modulo 2^32 on int64 values below 2^32 (no int64 overflow: the constant in two 16-bit halves)."""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+
+def _mix32(x: torch.Tensor) -> torch.Tensor:
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def sr_bits(n: int, t: torch.Tensor, seed: int, device=None) -> tuple:
+    """The 16 rounding bits of ``m`` and of ``v`` for the elements ``0 .. n-1`` at device step ``t`` (int64
+    tensors), as the bf16-state pass of ``optim_step_`` draws them: ``key = mix(seed ^ mix(t))``,
+    ``h = mix(lo32(i) ^ (hi32(i) * 0x9e3779b9) ^ key)``, ``m`` takes ``h & 0xffff`` and ``v`` ``h >> 16``
+    (torch integer ops, int64 masked to 32 bits; the definition is in ``csrc/kernels/optim.hip``)."""
+    device = t.device if device is None else device
+    key = _mix32((_mix32(t.reshape(()).to(device=device, dtype=torch.int64) & 0xFFFFFFFF)) ^ int(seed))
+    i = torch.arange(n, dtype=torch.int64, device=device)
+    h = _mix32((i & 0xFFFFFFFF) ^ _mul32((i >> 32) & 0xFFFFFFFF, 0x9E3779B9) ^ key)
+    return h & 0xFFFF, h >> 16
+
+
+def sr_bf16(x: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
+    """fp32 ``x`` rounded stochastically to bfloat16 with the 16 bits ``r`` (int64): the upper half of
+    ``bits(x) + r`` where ``x`` is finite, round-to-nearest (which keeps NaN and inf) elsewhere."""
+    bits = x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    up = (bits + r) >> 16
+    up = torch.where(up >= 0x8000, up - 0x10000, up).to(torch.int16).view(torch.bfloat16)
+    return torch.where(torch.isfinite(x), up, x.to(torch.bfloat16))
+
+
 class OptimGroups:
     """Parameter groups of ``AllReduceOutput.optim_step_(groups=...)``: the
     flat buffer cut into segments and one row of scalars per group, all in
@@ -266,7 +300,7 @@ class AllReduceOutput:
                     lr: float, *, weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
                     betas: tuple = (0.9, 0.999), eps: float = 1e-8, shadow: Optional[torch.Tensor] = None,
                     max_norm: Optional[float] = None, norm_ws: Optional[torch.Tensor] = None,
-                    nt: bool = False, groups: Optional[OptimGroups] = None) -> torch.Tensor:
+                    nt: bool = False, groups: Optional[OptimGroups] = None, seed: int = 0) -> torch.Tensor:
         """One optimizer step of the flat fp32 parameters ``p`` from this
         round, in one fused pass on the GPU: per element ``g = sum / count``,
         then ``kind="sgd"`` (``torch.optim.SGD``: weight decay into ``g``,
@@ -299,7 +333,17 @@ class AllReduceOutput:
         rows when the pass runs: ``lr`` and ``weight_decay`` are then not used
         (nor ``nt``).  A group whose learning rate is 0 advances ``m`` / ``v``
         and leaves ``p`` where it is (times its decay of 1); the shadow is
-        still written.  Returns ``p``."""
+        still written.
+
+        ``m`` and ``v`` may be bfloat16 instead (both, never one): they are
+        widened exactly, the update runs in fp32 as above, ``p`` and the
+        shadow come from the unrounded new moments, and only the stores of
+        ``m`` and ``v`` are rounded -- stochastically (``sr_bf16``), with the
+        bits of ``sr_bits``: a function of the element's index, ``t`` and
+        ``seed`` alone (the definition is at the top of the bf16 code in
+        ``csrc/kernels/optim.hip``), so ranks that share a seed round alike
+        and a replayed capture draws new bits each time.  ``nt`` is not
+        offered with bfloat16 state.  Returns ``p``."""
         self.wait()
         if kind not in ("sgd", "adamw"):
             raise ValueError(f"optim_step_: kind={kind!r} (sgd or adamw)")
@@ -308,9 +352,21 @@ class AllReduceOutput:
         if d.dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"optim_step_: a float32 or bfloat16 sum, not {d.dtype}")
         state =[("m", m)] + ([("v", v)] if adam else [])
-        for name, s in [("p", p)] + state:
-            if s is None or not self._flat_ok(s, torch.float32, align=1):
-                raise ValueError(f"optim_step_: {name} must be contiguous float32 of the round's size and device")
+        sdt = m.dtype if m is not None else torch.float32
+        if sdt not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"optim_step_: m and v are float32 or bfloat16, not {sdt}")
+        if adam and v is not None and v.dtype != sdt:
+            raise ValueError(f"optim_step_: m is {sdt} and v is {v.dtype}; they must agree")
+        bf_state = sdt == torch.bfloat16
+        if bf_state and nt:
+            raise ValueError("optim_step_: nt=True is not offered with bfloat16 state")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 32:
+            raise ValueError(f"optim_step_: seed={seed} is not an unsigned 32-bit value")
+        for name, s, dt in [("p", p, torch.float32)] + [(n, s, sdt) for n, s in state]:
+            if s is None or not self._flat_ok(s, dt, align=1):
+                raise ValueError(f"optim_step_: {name} must be contiguous {str(dt)[6:]} of the round's size and "
+                                 "device")
         if shadow is not None and not self._flat_ok(shadow, torch.bfloat16, align=1):
             raise ValueError("optim_step_: shadow must be contiguous bfloat16 of p's size and device")
         if t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device:
@@ -321,7 +377,8 @@ class AllReduceOutput:
             raise ValueError(f"optim_step_: the groups cover {groups.numel} elements on {groups.rows.device}, the "
                              f"round has {d.numel()} on {d.device}")
         if d.is_cuda:
-            if not (self._feeds_count_pass() and all(self._flat_ok(s, torch.float32) for _, s in [("p", p)] + state)
+            if not (self._feeds_count_pass() and self._flat_ok(p, torch.float32)
+                    and all(self._flat_ok(s, sdt) for _, s in state)
                     and (shadow is None or self._flat_ok(shadow, torch.bfloat16))):
                 raise ValueError("optim_step_: the fused pass needs a float32 or bfloat16 sum with its per-chunk "
                                  "counts (not expanded) and 16-B aligned buffers")
@@ -338,19 +395,25 @@ class AllReduceOutput:
                                           groups.host_seg_group, groups.ngroups,
                                           torch.cuda.current_stream(d.device).cuda_stream, momentum=momentum,
                                           nesterov=nesterov, beta1=betas[0], beta2=betas[1], eps=eps,
-                                          max_norm=max_norm if max_norm is not None else 0.0)
+                                          max_norm=max_norm if max_norm is not None else 0.0,
+                                          state_dtype=DTYPE_NAME[sdt], seed=seed)
                 return p
             load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
                                shadow.data_ptr() if shadow is not None else 0, d.data_ptr(), DTYPE_NAME[d.dtype],
                                table, t.data_ptr(), sq.data_ptr() if sq is not None else 0,
                                torch.cuda.current_stream(d.device).cuda_stream, bool(nt), lr=lr,
                                weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, beta1=betas[0],
-                               beta2=betas[1], eps=eps, max_norm=max_norm if max_norm is not None else 0.0)
+                               beta2=betas[1], eps=eps, max_norm=max_norm if max_norm is not None else 0.0,
+                               state_dtype=DTYPE_NAME[sdt], seed=seed)
             return p
         # the same formulas as torch operations (count-0 elements keep everything)
         keep = (self.count <= 0).view_as(p)
         g = self.mean(dtype=torch.float32) if d.dtype != torch.float32 else self.mean()
         g = g.view_as(p)
+        if bf_state:
+            # widened exactly; the formulas run in fp32 and only what is stored into m and v is rounded
+            m_st, v_st, m, v = m, v, m.float(), v.float() if adam else None
+            r_m, r_v = sr_bits(p.numel(), t, seed, p.device)
         if max_norm is not None:
             sq = self.sqnorm(norm_ws)
             g = g * torch.clamp(max_norm / (sq.sqrt() + 1e-6), max=1.0)
@@ -366,7 +429,6 @@ class AllReduceOutput:
                 vn = (v * b2).addcmul_(g, g, value=1 - b2)
                 nss = -(lr_v / (1 - b1 ** tf))
                 pn = torch.where(moves, pd.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(eps / nss)), pd)
-                v.copy_(torch.where(keep, v, vn))
             else:
                 g = torch.addcmul(g, p, wd)
                 mn = (m * momentum).add_(g)
@@ -381,12 +443,18 @@ class AllReduceOutput:
             # into the denominator as AdamW(capturable=True) and the kernel spell it
             nss = -(lr / (1 - b1 ** tf))
             pn = pn.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(eps / nss))
-            v.copy_(torch.where(keep, v, vn))
         else:
             g = g.add(p, alpha=weight_decay)
             mn = (m * momentum).add_(g)
             pn = p.add(g.add(mn, alpha=momentum) if nesterov else mn, alpha=-lr)
-        m.copy_(torch.where(keep, m, mn))
+        if bf_state:
+            m_st.copy_(torch.where(keep, m_st, sr_bf16(mn, r_m.view_as(mn))))
+            if adam:
+                v_st.copy_(torch.where(keep, v_st, sr_bf16(vn, r_v.view_as(vn))))
+        else:
+            m.copy_(torch.where(keep, m, mn))
+            if adam:
+                v.copy_(torch.where(keep, v, vn))
         p.copy_(torch.where(keep, p, pn))
         if shadow is not None:
             shadow.copy_(torch.where(keep.view_as(shadow), shadow, p.view_as(shadow).to(shadow.dtype)))

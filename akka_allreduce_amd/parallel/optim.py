@@ -28,6 +28,15 @@ that the pass reads when it runs (``data.OptimGroups``): biases and norm
 scales can stay out of the decay, and ``set_lr`` between two replays of a
 captured step changes its learning rate.  Betas, eps, momentum and the clip
 norm stay per optimizer.
+
+``state_dtype=torch.bfloat16`` keeps the moments ``m`` and ``v`` in bf16: half
+the optimizer memory and 8 (AdamW) or 4 (SGD) bytes per element less for the
+pass to move.  The pass widens them, updates in fp32, takes the parameters and
+the shadow from the unrounded moments and rounds only what it stores into
+``m`` and ``v`` -- stochastically, because a nearest-rounded bf16 ``v`` stops
+moving (docs/DESIGN.md).  The rounding bits are a function of the element's
+index, the device step and ``seed``: every rank must use the same seed (the
+default, 0, is), or their parameters drift apart.
 """
 from __future__ import annotations
 
@@ -39,6 +48,7 @@ from ..data import AllReduceOutput, OptimGroups, sqnorm_workspace
 from .dp import AllreduceFn, GradientBucket
 
 _GROUP_KEYS = ("params", "weight_decay", "lr_scale")
+_STATE_DTYPES = (torch.float32, torch.bfloat16)
 
 
 class _FusedOptimizer:
@@ -46,17 +56,23 @@ class _FusedOptimizer:
     hyper: Tuple[str, ...] = ()  # the attributes ``optim_step_`` takes as keywords
     needs_round = True  # without an allreduce: the bucket's round of one contributor
 
-    def __init__(self, bucket: GradientBucket, max_grad_norm: Optional[float]):
+    def __init__(self, bucket: GradientBucket, max_grad_norm: Optional[float],
+                 state_dtype: torch.dtype = torch.float32, seed: int = 0):
         if bucket.pflat is None or bucket.pflat.dtype != torch.float32 or bucket.flat.dtype != torch.float32:
             raise ValueError(f"{type(self).__name__}: needs GradientBucket(flatten_params=True) with float32 "
                              "parameters")
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError(f"max_grad_norm={max_grad_norm}: a positive norm, or None")
+        if state_dtype not in _STATE_DTYPES:
+            raise ValueError(f"{type(self).__name__}: state_dtype={state_dtype} (torch.float32 or torch.bfloat16)")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 32:
+            raise ValueError(f"{type(self).__name__}: seed={seed!r}, an integer in [0, 2**32)")
         self.bucket = bucket
         self.max_grad_norm = max_grad_norm
+        self.state_dtype, self.seed = state_dtype, seed
         dev = bucket.pflat.device
         # allocated once: a captured step bakes these pointers in
-        self.m = torch.zeros_like(bucket.pflat)
+        self.m = torch.zeros_like(bucket.pflat, dtype=state_dtype)
         self.v: Optional[torch.Tensor] = None
         self.t = torch.zeros(1, dtype=torch.int32, device=dev)
         self.norm_ws = sqnorm_workspace(dev) if max_grad_norm is not None else None
@@ -179,14 +195,18 @@ class _FusedOptimizer:
         """The optimizer's state with cloned tensors (``t`` is read from the device: a host sync)."""
         return {"kind": self.kind, "numel": self.bucket.numel, "t": int(self.t), "m": self.m.clone(),
                 "v": None if self.v is None else self.v.clone(), "hyper": self._hyper_dict(), "lr": self._lr,
-                "param_groups": self.param_groups}
+                "param_groups": self.param_groups, "state_dtype": self.state_dtype, "seed": self.seed}
 
     def load_state_dict(self, d: Dict[str, Any]) -> None:
         """Load a ``state_dict`` of an optimizer of the same kind, size and group layout.  Everything is copied
         IN PLACE: no address changes, so a captured step stays valid.  The hyper-parameters that are launch
         arguments (betas, eps, momentum, the clip norm; without ``device_lr`` the weight decay too) must match
         the ones this optimizer was built with -- a captured step has them baked in; the groups' weight decay
-        and lr scale and the uploaded learning rate are taken from ``d`` and the rows written again."""
+        and lr scale and the uploaded learning rate are taken from ``d`` and the rows written again.
+        ``seed`` is a launch argument too and must match (a dict without one was saved with seed 0).
+
+        ``m`` and ``v`` may be float32 or bfloat16 whatever this optimizer's ``state_dtype``: float32 into
+        bfloat16 state rounds to nearest, once; bfloat16 into float32 state is exact.  Any other dtype raises."""
         if d.get("kind") != self.kind:
             raise ValueError(f"load_state_dict: kind {d.get('kind')!r}, this optimizer is {self.kind!r}")
         if d.get("numel") != self.bucket.numel:
@@ -210,10 +230,13 @@ class _FusedOptimizer:
         if not self.device_lr and (theirs[0]["lr_scale"] != 1.0 or theirs[0]["weight_decay"] != self.weight_decay):
             raise ValueError("load_state_dict: the group's lr_scale / weight_decay differ; without device_lr they "
                              "are launch arguments")
+        if d.get("seed", 0) != self.seed:
+            raise ValueError(f"load_state_dict: seed={d.get('seed', 0)!r}, this optimizer was built with {self.seed!r} "
+                             "(a launch argument)")
         if (d.get("v") is None) != (self.v is None):
             raise ValueError("load_state_dict: v does not match the optimizer's kind")
         for name, dst in (("m", self.m), ("v", self.v)):
-            if dst is not None and (d[name].shape != dst.shape or d[name].dtype != dst.dtype):
+            if dst is not None and (d[name].shape != dst.shape or d[name].dtype not in _STATE_DTYPES):
                 raise ValueError(f"load_state_dict: {name} is {d[name].dtype} {tuple(d[name].shape)}")
         self.m.copy_(d["m"])
         if self.v is not None:
@@ -247,7 +270,8 @@ class _FusedOptimizer:
             self.set_lr(lr)
         self.t.add_(1)
         out.optim_step_(self.kind, bucket.pflat, self.m, self.v, self.t, lr, shadow=shadow, max_norm=self.max_grad_norm,
-                        norm_ws=self.norm_ws, groups=self.groups, **{k: getattr(self, k) for k in self.hyper})
+                        norm_ws=self.norm_ws, groups=self.groups, seed=self.seed,
+                        **{k: getattr(self, k) for k in self.hyper})
 
 
 class FusedSGD(_FusedOptimizer):
@@ -259,18 +283,22 @@ class FusedSGD(_FusedOptimizer):
     over parameters of the bucket, each in at most one group; the parameters
     listed nowhere form a last group with the defaults.  A group steps with
     ``lr * lr_scale``.  ``device_lr=True`` alone is one group; either keeps the
-    learning rate in device memory (``set_lr``)."""
+    learning rate in device memory (``set_lr``).
+
+    ``state_dtype=torch.bfloat16`` keeps the momentum in bf16, stored with
+    stochastic rounding; ``seed`` keys the rounding bits and must be the same
+    on every rank."""
 
     kind, hyper = "sgd", ("momentum", "nesterov", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, momentum: float = 0.9, nesterov: bool = False,
                  weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, param_groups=None,
-                 device_lr: bool = False):
+                 device_lr: bool = False, state_dtype: torch.dtype = torch.float32, seed: int = 0):
         if momentum < 0 or weight_decay < 0:
             raise ValueError("FusedSGD: momentum and weight_decay are >= 0")
         if nesterov and momentum <= 0:
             raise ValueError("FusedSGD: Nesterov momentum needs momentum > 0")
-        super().__init__(bucket, max_grad_norm)
+        super().__init__(bucket, max_grad_norm, state_dtype, seed)
         self.momentum, self.nesterov, self.weight_decay = float(momentum), bool(nesterov), float(weight_decay)
         self._init_groups(param_groups, device_lr)
 
@@ -278,16 +306,17 @@ class FusedSGD(_FusedOptimizer):
 class FusedAdamW(_FusedOptimizer):
     """``torch.optim.AdamW(betas, eps, weight_decay)`` on a
     ``GradientBucket(flatten_params=True)``, fused into the averaging.
-    ``param_groups`` / ``device_lr`` as for ``FusedSGD``."""
+    ``param_groups`` / ``device_lr`` / ``state_dtype`` / ``seed`` as for
+    ``FusedSGD`` (bf16 state: ``m`` and ``v``)."""
 
     kind, hyper = "adamw", ("betas", "eps", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, max_grad_norm: Optional[float] = None, param_groups=None,
-                 device_lr: bool = False):
+                 device_lr: bool = False, state_dtype: torch.dtype = torch.float32, seed: int = 0):
         if not (0 <= betas[0] < 1 and 0 <= betas[1] < 1) or eps < 0 or weight_decay < 0:
             raise ValueError("FusedAdamW: betas in [0, 1), eps and weight_decay >= 0")
-        super().__init__(bucket, max_grad_norm)
-        self.v = torch.zeros_like(bucket.pflat)
+        super().__init__(bucket, max_grad_norm, state_dtype, seed)
+        self.v = torch.zeros_like(self.m)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self._init_groups(param_groups, device_lr)

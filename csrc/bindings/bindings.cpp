@@ -1082,26 +1082,28 @@ PYBIND11_MODULE(_native, m) {
   m.def("count_optim", [](const std::string& kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow,
                           uintptr_t src, const std::string& src_dtype, const CountsArgs& table, uintptr_t t,
                           uintptr_t sq, uintptr_t stream, bool nt, double lr, double weight_decay, double momentum,
-                          bool nesterov, double beta1, double beta2, double eps, double max_norm) {
+                          bool nesterov, double beta1, double beta2, double eps, double max_norm,
+                          const std::string& state_dtype, uint32_t seed) {
     AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim: kind is 'sgd' or 'adamw'");
     const OptimSpec o{kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD, lr, weight_decay, momentum, nesterov,
                       beta1, beta2, eps, max_norm};
-    launch_count_optim(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<float*>(mom),
-                       reinterpret_cast<float*>(v), reinterpret_cast<void*>(shadow),
+    launch_count_optim(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom),
+                       reinterpret_cast<void*>(v), parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
                        reinterpret_cast<const void*>(src), parse_dtype(src_dtype), counts_table(table), o,
-                       reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), nt);
+                       reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed, nt);
   }, py::arg("kind"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("src"),
      py::arg("src_dtype"), py::arg("table"), py::arg("t"), py::arg("sq"), py::arg("stream") = 0,
      py::arg("nt") = false, py::kw_only(), py::arg("lr"), py::arg("weight_decay") = 0.0, py::arg("momentum") = 0.0,
      py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-8,
-     py::arg("max_norm") = 0.0);
+     py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("seed") = 0u);
   // seg_end / seg_group / rows: device tables; host_seg_end / host_seg_group: their host copies (checked here)
   m.def("count_optim_groups", [](const std::string& kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow,
                                  uintptr_t src, const std::string& src_dtype, const CountsArgs& table, uintptr_t t,
                                  uintptr_t sq, uintptr_t seg_end, uintptr_t seg_group, uintptr_t rows,
                                  const std::vector<int64_t>& host_seg_end, const std::vector<int32_t>& host_seg_group,
                                  int32_t ngroups, uintptr_t stream, double momentum, bool nesterov, double beta1,
-                                 double beta2, double eps, double max_norm) {
+                                 double beta2, double eps, double max_norm, const std::string& state_dtype,
+                                 uint32_t seed) {
     AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim_groups: kind is 'sgd' or 'adamw'");
     AKKA_CHECK(!host_seg_end.empty() && host_seg_end.size() == host_seg_group.size(),
                "count_optim_groups: one group per segment");
@@ -1115,15 +1117,16 @@ PYBIND11_MODULE(_native, m) {
     g.ngroups = ngroups;
     g.host_seg_end = host_seg_end.data();
     g.host_seg_group = host_seg_group.data();
-    launch_count_optim_groups(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<float*>(mom),
-                              reinterpret_cast<float*>(v), reinterpret_cast<void*>(shadow),
+    launch_count_optim_groups(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom),
+                              reinterpret_cast<void*>(v), parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
                               reinterpret_cast<const void*>(src), parse_dtype(src_dtype), counts_table(table), o, g,
-                              reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq));
+                              reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed);
   }, py::arg("kind"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("src"),
      py::arg("src_dtype"), py::arg("table"), py::arg("t"), py::arg("sq"), py::arg("seg_end"), py::arg("seg_group"),
      py::arg("rows"), py::arg("host_seg_end"), py::arg("host_seg_group"), py::arg("ngroups"), py::arg("stream") = 0,
      py::kw_only(), py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9,
-     py::arg("beta2") = 0.999, py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0);
+     py::arg("beta2") = 0.999, py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0,
+     py::arg("state_dtype") = "float32", py::arg("seed") = 0u);
   m.def("count_sqnorm", [](uintptr_t sq, uintptr_t src, const std::string& src_dtype, const CountsArgs& table,
                            uintptr_t part, uintptr_t ticket, uintptr_t stream) {
     launch_count_sqnorm(as_stream(stream), reinterpret_cast<float*>(sq), reinterpret_cast<const void*>(src),

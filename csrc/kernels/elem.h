@@ -2,7 +2,8 @@
 // element type, the fp32 accumulate of a vector, the pack of the accumulators
 // and the scalar conversions.  Sums accumulate in fp32; bf16 is rounded in one
 // place (Elt<bf16_t>::from_f), so a sum is the same bits whichever kernel made
-// it.  Only to be included by .hip translation units.
+// it; the one other rounding is sr_bf16 below, the stochastic one of the
+// optimizer's bf16 moments.  Only to be included by .hip translation units.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,5 +66,39 @@ struct Elt<bf16_t> {
   __device__ __forceinline__ static float load1(const char* p) { return to_f(*reinterpret_cast<const bf16_t*>(p)); }
   __device__ __forceinline__ static void store1(char* p, float v) { *reinterpret_cast<bf16_t*>(p) = from_f(v); }
 };
+
+// Element q of a unit's vectors widened to fp32, bit for bit (Elt<T>::add onto
+// a zero would turn -0 into +0).  q is a constant after unrolling.
+template <typename T>
+__device__ __forceinline__ float unit_elem(const v4u* u, int q) {
+  if constexpr (Elt<T>::kPerVec == 8) {
+    const uint32_t w = u[q >> 3][(q >> 1) & 3];
+    return __uint_as_float((q & 1) ? (w & 0xffff0000u) : (w << 16));
+  } else {
+    return __uint_as_float(u[q >> 2][q & 3]);
+  }
+}
+
+// Stochastic rounding of fp32 to bf16 with 16 random bits r: the bits below
+// the bf16 mantissa plus r carry into it with probability (those bits) / 2^16,
+// so the expectation of the result is x.  A finite x that rounds up past the
+// largest bf16 becomes inf, as under round-to-nearest.  The add would carry a
+// NaN's payload into the exponent and the sign, so a non-finite x takes the
+// NaN-preserving codec above.  (The definition of r: optim.hip.)
+__device__ __forceinline__ bf16_t sr_bf16(float x, uint32_t r) {
+  const uint32_t b = __float_as_uint(x);
+  if ((b & 0x7f800000u) == 0x7f800000u) return Elt<bf16_t>::from_f(x);
+  return bf16_t((b + (r & 0xffffu)) >> 16);
+}
+
+// The 32-bit mixer of the rounding bits (two multiplies, three xor-shifts; a bijection).
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
 
 }  // namespace akka

@@ -49,6 +49,11 @@ void launch_count_mean(hipStream_t s, void* dst, const void* src, const CountsTa
 // are.  `t`: the step, one int32 on the device (AdamW's bias corrections).
 // src_dt: F32 or BF16.  nt: nontemporal instead of plain accesses (slower
 // where measured; for the comparison in bench/fused_opt.py).
+// state_dt: the element type of m and v, F32 or BF16.  BF16 moments are widened
+// on load, updated in fp32 and stored with stochastic rounding, the bits drawn
+// from (element index, *t, seed) -- the definition is in optim.hip; p and the
+// shadow come from the unrounded moments.  `t` is then needed for SGD too, and
+// nt is refused.  seed is not used with F32 state.
 enum class OptimKind : int32_t { SGD = 0, AdamW = 1 };
 struct OptimSpec {
   OptimKind kind = OptimKind::SGD;
@@ -58,8 +63,9 @@ struct OptimSpec {
   double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;  // AdamW
   double max_norm = 0;                            // used with sq
 };
-void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
-                        const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq, bool nt = false);
+void launch_count_optim(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow, const void* src,
+                        DType src_dt, const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq,
+                        uint32_t seed = 0, bool nt = false);
 // The same step with parameter groups and a device-resident learning rate.
 // The flat buffer is cut into `nseg` segments: seg_end (device, int64) holds
 // their ascending exclusive ends, the last one S, seg_group (device, int32)
@@ -78,9 +84,9 @@ struct OptimGroups {
   const int64_t* host_seg_end = nullptr;
   const int32_t* host_seg_group = nullptr;
 };
-void launch_count_optim_groups(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src,
-                               DType src_dt, const CountsTable& ct, const OptimSpec& o, const OptimGroups& g,
-                               const int32_t* t, const float* sq);
+void launch_count_optim_groups(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow,
+                               const void* src, DType src_dt, const CountsTable& ct, const OptimSpec& o,
+                               const OptimGroups& g, const int32_t* t, const float* sq, uint32_t seed = 0);
 // sq[0] = sum over the elements whose count is > 0 of (src / count)^2.  part:
 // fp32 [count_sqnorm_partials()] workspace; ticket: one uint32 zeroed once
 // (each launch leaves it zero again).  Deterministic for a given shape.

@@ -6,9 +6,10 @@
 // clip coefficient, then torch's update (torch.optim.SGD with dampening 0,
 // torch.optim.AdamW), operation by operation in the order and with the
 // roundings of torch's own element-wise kernels (update_one below), so torch
-// in fp32 is a comparator that differs in the last bits only.  p, m, v are
-// fp32; the sum is fp32 or bf16 (a compressed wire's sum, read wide into
-// fp32); an optional bf16 shadow receives bf16(p_new) from the same pass.
+// in fp32 is a comparator that differs in the last bits only.  p is fp32; m
+// and v are fp32, or bf16 stored with stochastic rounding (below, in front of
+// update_range); the sum is fp32 or bf16 (a compressed wire's sum, read wide
+// into fp32); an optional bf16 shadow receives bf16(p_new) from the same pass.
 //
 // Count 0 means MISSING, not zero: a chunk no contributor reached leaves p, m,
 // v and the shadow untouched -- the region is skipped before any load.  With
@@ -35,7 +36,9 @@
 // 2.7-4.2 TB/s in every variant (AdamW + shadow from an fp32 sum: 237 us
 // against 309 us), so unlike pack_bf16 this pass uses plain accesses at every
 // size; `nt` is kept so that bench/fused_opt.py can repeat the comparison
-// (table in profiles/r08/fused_opt/README.md).
+// (table in profiles/r08/fused_opt/README.md).  bf16 moments take 4 B per
+// element off SGD and 8 B off AdamW, and the time follows the bytes
+// (profiles/r10/bf16_state/README.md).
 //
 // count_optim_groups: the same pass with per-group weight decay and learning
 // rate, both read from a small device table when the kernel runs (below, at
@@ -137,26 +140,72 @@ __device__ __forceinline__ void update_one(float g, float& p, float& m, float& v
   }
 }
 
+// bf16 moments (TM = bf16_t): m and v are stored as bf16 and rounded
+// STOCHASTICALLY.  Round-to-nearest is not an option: v = b2 * v + (1 - b2) *
+// g^2 moves by 2^-10 of itself per step at b2 = 0.999 and a bf16 ulp is 2^-8 of
+// the value, so a nearest-rounded v stops where the increment falls under half
+// an ulp (g = 1: at 0.25 instead of 0.632 after 1000 steps).  With the rounding
+// below the expectation of the stored value is the fp32 value.
+//
+// Definition (x fp32, r 16 bits; the tests carry their own copy of it):
+//   sr(x, r) = uint16((bits(x) + r) >> 16)   for finite x,
+//              Elt<bf16_t>::from_f(x)        otherwise          (sr_bf16, elem.h)
+//   mix(x)   : x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+//              x ^= x >> 16                   on uint32          (mix32, elem.h)
+//   key      = mix(seed ^ mix(uint32(*t)))
+//   h(i)     = mix(uint32(i) ^ (uint32(i >> 32) * 0x9e3779b9) ^ key)
+//              for the element's flat index i (int64) in the bucket
+//   m takes r = h & 0xffff, v takes r = h >> 16.
+// The bits depend on (index, device step, seed) and on nothing else: every
+// rank of a data-parallel job rounds alike (with the same seed), a captured
+// step draws new bits on each replay (*t is read when the kernel runs), and
+// neither the grid nor the chunk geometry matters.  The key is wave-uniform,
+// computed once per kernel.
+//
+// The pass widens m and v exactly on load, runs update_one on the fp32 values
+// and computes p and the shadow from the UNROUNDED new moments: only the stores
+// of m and v go through sr, so p is bitwise what the fp32-state pass gives from
+// the widened state.  A unit is still 8 elements, m and v one 16-B vector each.
+// Nontemporal accesses are not offered with bf16 moments (the launcher refuses).
+__device__ __forceinline__ uint32_t sr_key(uint32_t seed, const int32_t* t) {
+  return mix32(seed ^ mix32(uint32_t(*t)));
+}
+
+// The index's part of h: everything but the last mix, for an index whose low 32 bits are lo.
+__device__ __forceinline__ uint32_t sr_hi(int64_t i, uint32_t key) {
+  return (uint32_t(uint64_t(i) >> 32) * 0x9e3779b9u) ^ key;
+}
+
 // The elements [s, e) of one count region (fv: its count) with one set of
 // scalars: scalar head and tail outside the 8-aligned body, units in between,
-// split over the gridDim.y workgroups that share the region.
-template <typename TS, bool ADAM, bool SHADOW, bool NT, bool GROUPS = false>
-__device__ __forceinline__ void update_range(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+// split over the gridDim.y workgroups that share the region.  TM: the element
+// type of m and v; key: the rounding key (bf16 moments only).
+template <typename TS, typename TM, bool ADAM, bool SHADOW, bool NT, bool GROUPS = false>
+__device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restrict__ m, TM* __restrict__ v,
                                              bf16_t* __restrict__ shadow, const TS* __restrict__ src, int64_t s,
-                                             int64_t e, float fv, const OptimK& k, const Coef& c) {
+                                             int64_t e, float fv, const OptimK& k, const Coef& c, uint32_t key) {
+  constexpr bool SR = Elt<TM>::kPerVec == 8;  // bf16 moments, stored with stochastic rounding
+  static_assert(!(SR && NT), "bf16 moments have no nontemporal variant");
   constexpr int E = 8;                        // elements per unit
   constexpr int ES = Elt<TS>::kPerVec;        // elements per source vector
   constexpr int NS = E / ES;                  // source vectors per unit
   constexpr int NF = E / Elt<float>::kPerVec; // fp32 vectors per unit and stream
+  constexpr int NM = E / Elt<TM>::kPerVec;    // vectors of m (and of v) per unit
   int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first element 16-B aligned in every stream
   if (a > e) a = e;
   const int64_t nv = (e - a) / E;
   auto one = [&](int64_t i) {
-    float pi = p[i], mi = m[i], vi = ADAM ? v[i] : 0.f;
+    float pi = p[i], mi = Elt<TM>::to_f(m[i]), vi = ADAM ? Elt<TM>::to_f(v[i]) : 0.f;
     update_one<ADAM, GROUPS>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
     p[i] = pi;
-    m[i] = mi;
-    if constexpr (ADAM) v[i] = vi;
+    if constexpr (SR) {
+      const uint32_t h = mix32(uint32_t(i) ^ sr_hi(i, key));
+      m[i] = sr_bf16(mi, h & 0xffffu);
+      if constexpr (ADAM) v[i] = sr_bf16(vi, h >> 16);
+    } else {
+      m[i] = mi;
+      if constexpr (ADAM) v[i] = vi;
+    }
     if constexpr (SHADOW) shadow[i] = Elt<bf16_t>::from_f(pi);
   };
   if (blockIdx.y == 0) {
@@ -174,7 +223,7 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, float* __res
     else *q = x;
   };
   struct Unit {
-    v4u s[NS], p[NF], m[NF], v[NF];
+    v4u s[NS], p[NF], m[NM], v[NM];
   };
   auto load = [&](int64_t at) {
     Unit u;
@@ -183,10 +232,10 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, float* __res
 #pragma unroll
     for (int q = 0; q < NF; ++q) u.p[q] = ld(p4 + at * NF + q);
 #pragma unroll
-    for (int q = 0; q < NF; ++q) u.m[q] = ld(m4 + at * NF + q);
+    for (int q = 0; q < NM; ++q) u.m[q] = ld(m4 + at * NM + q);
     if constexpr (ADAM) {
 #pragma unroll
-      for (int q = 0; q < NF; ++q) u.v[q] = ld(v4 + at * NF + q);
+      for (int q = 0; q < NM; ++q) u.v[q] = ld(v4 + at * NM + q);
     }
     return u;
   };
@@ -196,21 +245,44 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, float* __res
     for (int q = 0; q < E; ++q) g[q] = 0.f;
 #pragma unroll
     for (int q = 0; q < NS; ++q) Elt<TS>::add(reinterpret_cast<float(&)[ES]>(g[q * ES]), u.s[q]);
+    if constexpr (SR) {
+      // the unit's first element is a multiple of 8: its elements differ in the low three bits alone
+      const int64_t i0 = a + at * E;
+      const uint32_t lo = uint32_t(i0), hi = sr_hi(i0, key);
+      uint32_t mo[E], vo[E];
 #pragma unroll
-    for (int q = 0; q < E; ++q) {
-      float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = __uint_as_float(u.m[q >> 2][q & 3]);
-      float vi = ADAM ? __uint_as_float(u.v[q >> 2][q & 3]) : 0.f;
-      update_one<ADAM, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
-      pn[q] = pi;
-      u.p[q >> 2][q & 3] = __float_as_uint(pi);
-      u.m[q >> 2][q & 3] = __float_as_uint(mi);
-      if constexpr (ADAM) u.v[q >> 2][q & 3] = __float_as_uint(vi);
-    }
+      for (int q = 0; q < E; ++q) {
+        float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = unit_elem<TM>(u.m, q);
+        float vi = ADAM ? unit_elem<TM>(u.v, q) : 0.f;
+        update_one<ADAM, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
+        pn[q] = pi;
+        u.p[q >> 2][q & 3] = __float_as_uint(pi);
+        const uint32_t h = mix32((lo | uint32_t(q)) ^ hi);
+        mo[q] = sr_bf16(mi, h & 0xffffu);
+        if constexpr (ADAM) vo[q] = sr_bf16(vi, h >> 16);
+      }
 #pragma unroll
-    for (int q = 0; q < NF; ++q) {
-      st(u.p[q], p4 + at * NF + q);
-      st(u.m[q], m4 + at * NF + q);
-      if constexpr (ADAM) st(u.v[q], v4 + at * NF + q);
+      for (int q = 0; q < NF; ++q) st(u.p[q], p4 + at * NF + q);
+      st(v4u{mo[0] | (mo[1] << 16), mo[2] | (mo[3] << 16), mo[4] | (mo[5] << 16), mo[6] | (mo[7] << 16)}, m4 + at);
+      if constexpr (ADAM)
+        st(v4u{vo[0] | (vo[1] << 16), vo[2] | (vo[3] << 16), vo[4] | (vo[5] << 16), vo[6] | (vo[7] << 16)}, v4 + at);
+    } else {
+#pragma unroll
+      for (int q = 0; q < E; ++q) {
+        float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = __uint_as_float(u.m[q >> 2][q & 3]);
+        float vi = ADAM ? __uint_as_float(u.v[q >> 2][q & 3]) : 0.f;
+        update_one<ADAM, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
+        pn[q] = pi;
+        u.p[q >> 2][q & 3] = __float_as_uint(pi);
+        u.m[q >> 2][q & 3] = __float_as_uint(mi);
+        if constexpr (ADAM) u.v[q >> 2][q & 3] = __float_as_uint(vi);
+      }
+#pragma unroll
+      for (int q = 0; q < NF; ++q) {
+        st(u.p[q], p4 + at * NF + q);
+        st(u.m[q], m4 + at * NF + q);
+        if constexpr (ADAM) st(u.v[q], v4 + at * NF + q);
+      }
     }
     if constexpr (SHADOW) st(Elt<bf16_t>::pack(pn), h4 + at);
   };
@@ -227,15 +299,17 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, float* __res
   }
 }
 
-template <typename TS, bool ADAM, bool SHADOW, bool NT>
-__global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                             float* __restrict__ v, bf16_t* __restrict__ shadow,
+template <typename TS, typename TM, bool ADAM, bool SHADOW, bool NT>
+__global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__ p, TM* __restrict__ m,
+                                                             TM* __restrict__ v, bf16_t* __restrict__ shadow,
                                                              const TS* __restrict__ src,
                                                              const int32_t* __restrict__ counts, int64_t S,
                                                              int64_t step, int32_t N, int64_t C, int32_t kmax,
                                                              OptimK k, const int32_t* __restrict__ t,
-                                                             const float* __restrict__ sq) {
+                                                             const float* __restrict__ sq, uint32_t seed) {
   const Coef c = lr_coefficients<ADAM>(step_coefficients<ADAM>(k, t, sq), k.lr, k.eps);
+  uint32_t key = 0;
+  if constexpr (Elt<TM>::kPerVec == 8) key = sr_key(seed, t);
   const int64_t nregions = int64_t(N) * kmax;
   for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
     const int32_t j = int32_t(reg / kmax);
@@ -247,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
     const int64_t e = s + C < be ? s + C : be;
     const int32_t cnt = counts[reg];
     if (cnt <= 0) continue;  // missing: nothing of this region is loaded or stored
-    update_range<TS, ADAM, SHADOW, NT>(p, m, v, shadow, src, s, e, float(cnt), k, c);
+    update_range<TS, TM, ADAM, SHADOW, NT>(p, m, v, shadow, src, s, e, float(cnt), k, c, key);
   }
 }
 
@@ -259,14 +333,16 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
 // A region is walked by its intersections with the segments, each processed as
 // count_optim processes a region, with its group's row.  Everything that picks
 // the segment and the row is wave-uniform (scalar loads, scalar branches).
-template <typename TS, bool ADAM, bool SHADOW>
+template <typename TS, typename TM, bool ADAM, bool SHADOW>
 __global__ __launch_bounds__(kBlock) void count_optim_groups_kernel(
-    float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, bf16_t* __restrict__ shadow,
+    float* __restrict__ p, TM* __restrict__ m, TM* __restrict__ v, bf16_t* __restrict__ shadow,
     const TS* __restrict__ src, const int32_t* __restrict__ counts, int64_t S, int64_t step, int32_t N, int64_t C,
     int32_t kmax, OptimK k, const int32_t* __restrict__ t, const float* __restrict__ sq,
     const int64_t* __restrict__ seg_end, const int32_t* __restrict__ seg_group, const float4* __restrict__ rows,
-    int32_t nseg, int32_t G) {
+    int32_t nseg, int32_t G, uint32_t seed) {
   const StepCoef sc = step_coefficients<ADAM>(k, t, sq);
+  uint32_t key = 0;
+  if constexpr (Elt<TM>::kPerVec == 8) key = sr_key(seed, t);
   const int64_t nregions = int64_t(N) * kmax;
   for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
     const int32_t j = int32_t(reg / kmax);
@@ -299,8 +375,8 @@ __global__ __launch_bounds__(kBlock) void count_optim_groups_kernel(
         kg.wd = r.y;
         kg.lr = r.z;
         kg.decay = r.w;
-        update_range<TS, ADAM, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
-                                                    lr_coefficients<ADAM>(sc, r.z, k.eps));
+        update_range<TS, TM, ADAM, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
+                                                        lr_coefficients<ADAM>(sc, r.z, k.eps), key);
       }
       cur = ee;
     }
@@ -403,11 +479,15 @@ bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 
 
 }  // namespace
 
-void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src, DType src_dt,
-                        const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq, bool nt) {
+void launch_count_optim(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow, const void* src,
+                        DType src_dt, const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq,
+                        uint32_t seed, bool nt) {
   if (ct.S <= 0) return;
   const bool adam = o.kind == OptimKind::AdamW;
-  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)), "count_optim: null buffer");
+  const bool bf_state = state_dt == DType::BF16;
+  AKKA_CHECK(!(bf_state && nt), "count_optim: no nontemporal variant with bfloat16 state");
+  // bf16 state reads the step for its rounding key, whatever the kind
+  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)) && (!bf_state || t), "count_optim: null buffer");
   AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
              "count_optim: buffers must be 16-B aligned");
   ct.check("count_optim");
@@ -426,13 +506,15 @@ void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shado
   k.max_norm = float(o.max_norm);
   const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
   auto* h = static_cast<bf16_t*>(shadow);
-#define AKKA_OPT(TS, AD, SH, NTV)                                                                              \
-  hipLaunchKernelGGL((count_optim_kernel<TS, AD, SH, NTV>), dim3(grid, split), dim3(kBlock), 0, s, p, m, v, h, \
-                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, t, sq)
-#define AKKA_OPT_NT(TS, AD, SH)       \
-  do {                                \
-    if (nt) AKKA_OPT(TS, AD, SH, true); \
-    else AKKA_OPT(TS, AD, SH, false); \
+#define AKKA_OPT(TS, TM, AD, SH, NTV)                                                                           \
+  hipLaunchKernelGGL((count_optim_kernel<TS, TM, AD, SH, NTV>), dim3(grid, split), dim3(kBlock), 0, s, p,       \
+                     static_cast<TM*>(m), static_cast<TM*>(v), h, static_cast<const TS*>(src), ct.counts, ct.S, \
+                     ct.step, ct.N, ct.C, ct.kmax, k, t, sq, seed)
+#define AKKA_OPT_NT(TS, AD, SH)                          \
+  do {                                                   \
+    if (bf_state) AKKA_OPT(TS, bf16_t, AD, SH, false);   \
+    else if (nt) AKKA_OPT(TS, float, AD, SH, true);      \
+    else AKKA_OPT(TS, float, AD, SH, false);             \
   } while (0)
 #define AKKA_OPT_SH(TS, AD)                \
   do {                                     \
@@ -452,12 +534,14 @@ void launch_count_optim(hipStream_t s, float* p, float* m, float* v, void* shado
   check_launch("count_optim");
 }
 
-void launch_count_optim_groups(hipStream_t s, float* p, float* m, float* v, void* shadow, const void* src,
-                               DType src_dt, const CountsTable& ct, const OptimSpec& o, const OptimGroups& g,
-                               const int32_t* t, const float* sq) {
+void launch_count_optim_groups(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow,
+                               const void* src, DType src_dt, const CountsTable& ct, const OptimSpec& o,
+                               const OptimGroups& g, const int32_t* t, const float* sq, uint32_t seed) {
   if (ct.S <= 0) return;
   const bool adam = o.kind == OptimKind::AdamW;
-  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)), "count_optim_groups: null buffer");
+  const bool bf_state = state_dt == DType::BF16;
+  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)) && (!bf_state || t),
+             "count_optim_groups: null buffer");
   AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
              "count_optim_groups: buffers must be 16-B aligned");
   ct.check("count_optim_groups");
@@ -487,14 +571,20 @@ void launch_count_optim_groups(hipStream_t s, float* p, float* m, float* v, void
   const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
   auto* h = static_cast<bf16_t*>(shadow);
   const auto* rows = reinterpret_cast<const float4*>(g.rows);
-#define AKKA_OPTG(TS, AD, SH)                                                                                    \
-  hipLaunchKernelGGL((count_optim_groups_kernel<TS, AD, SH>), dim3(grid, split), dim3(kBlock), 0, s, p, m, v, h, \
-                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, t, sq,       \
-                     g.seg_end, g.seg_group, rows, g.nseg, g.ngroups)
-#define AKKA_OPTG_SH(TS, AD)            \
-  do {                                  \
-    if (shadow) AKKA_OPTG(TS, AD, true); \
-    else AKKA_OPTG(TS, AD, false);      \
+#define AKKA_OPTG(TS, TM, AD, SH)                                                                               \
+  hipLaunchKernelGGL((count_optim_groups_kernel<TS, TM, AD, SH>), dim3(grid, split), dim3(kBlock), 0, s, p,     \
+                     static_cast<TM*>(m), static_cast<TM*>(v), h, static_cast<const TS*>(src), ct.counts, ct.S, \
+                     ct.step, ct.N, ct.C, ct.kmax, k, t, sq, g.seg_end, g.seg_group, rows, g.nseg, g.ngroups,   \
+                     seed)
+#define AKKA_OPTG_TM(TS, AD, SH)                \
+  do {                                          \
+    if (bf_state) AKKA_OPTG(TS, bf16_t, AD, SH); \
+    else AKKA_OPTG(TS, float, AD, SH);          \
+  } while (0)
+#define AKKA_OPTG_SH(TS, AD)               \
+  do {                                     \
+    if (shadow) AKKA_OPTG_TM(TS, AD, true); \
+    else AKKA_OPTG_TM(TS, AD, false);      \
   } while (0)
   if (src_dt == DType::BF16) {
     if (adam) AKKA_OPTG_SH(bf16_t, true);
@@ -504,6 +594,7 @@ void launch_count_optim_groups(hipStream_t s, float* p, float* m, float* v, void
     else AKKA_OPTG_SH(float, false);
   }
 #undef AKKA_OPTG_SH
+#undef AKKA_OPTG_TM
 #undef AKKA_OPTG
   check_launch("count_optim_groups");
 }

@@ -328,12 +328,11 @@ class AllReduceOutput:
         accesses instead of plain ones (slower where measured: kept for
         ``bench/fused_opt.py``).
 
-        ``groups`` (``OptimGroups``) gives every segment of the buffer its
-        group's learning rate and weight decay, read from the groups' device
-        rows when the pass runs: ``lr`` and ``weight_decay`` are then not used
-        (nor ``nt``).  A group whose learning rate is 0 advances ``m`` / ``v``
-        and leaves ``p`` where it is (times its decay of 1); the shadow is
-        still written.
+        ``groups`` (``OptimGroups``) gives every segment its group's learning
+        rate and weight decay, read from the groups' device rows when the pass
+        runs, in place of ``lr`` and ``weight_decay`` (``nt`` is ignored).  A
+        group whose learning rate is 0 advances ``m`` / ``v`` and leaves ``p``
+        where it is; the shadow is still written.
 
         ``m`` and ``v`` may be bfloat16 instead (both, never one): they are
         widened exactly, the update runs in fp32 as above, ``p`` and the
@@ -386,25 +385,17 @@ class AllReduceOutput:
 
             sq = self.sqnorm(norm_ws) if max_norm is not None else None
             pc, table = counts_table(self.counts_per_chunk, self.geometry)
-            if groups is not None:
-                load().count_optim_groups(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
-                                          shadow.data_ptr() if shadow is not None else 0, d.data_ptr(),
-                                          DTYPE_NAME[d.dtype], table, t.data_ptr(),
-                                          sq.data_ptr() if sq is not None else 0, groups.seg_end.data_ptr(),
-                                          groups.seg_group.data_ptr(), groups.rows.data_ptr(), groups.host_seg_end,
-                                          groups.host_seg_group, groups.ngroups,
-                                          torch.cuda.current_stream(d.device).cuda_stream, momentum=momentum,
-                                          nesterov=nesterov, beta1=betas[0], beta2=betas[1], eps=eps,
-                                          max_norm=max_norm if max_norm is not None else 0.0,
-                                          state_dtype=DTYPE_NAME[sdt], seed=seed)
-                return p
+            # the tables stay alive in `groups` until the call returns; nt is not offered with groups
+            gr = None if groups is None else (groups.seg_end.data_ptr(), groups.seg_group.data_ptr(),
+                                              groups.rows.data_ptr(), groups.host_seg_end, groups.host_seg_group,
+                                              groups.ngroups)
             load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
                                shadow.data_ptr() if shadow is not None else 0, d.data_ptr(), DTYPE_NAME[d.dtype],
                                table, t.data_ptr(), sq.data_ptr() if sq is not None else 0,
-                               torch.cuda.current_stream(d.device).cuda_stream, bool(nt), lr=lr,
+                               torch.cuda.current_stream(d.device).cuda_stream, bool(nt) and groups is None, lr=lr,
                                weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, beta1=betas[0],
                                beta2=betas[1], eps=eps, max_norm=max_norm if max_norm is not None else 0.0,
-                               state_dtype=DTYPE_NAME[sdt], seed=seed)
+                               state_dtype=DTYPE_NAME[sdt], seed=seed, groups=gr)
             return p
         # the same formulas as torch operations (count-0 elements keep everything)
         keep = (self.count <= 0).view_as(p)
@@ -417,36 +408,30 @@ class AllReduceOutput:
         if max_norm is not None:
             sq = self.sqnorm(norm_ws)
             g = g * torch.clamp(max_norm / (sq.sqrt() + 1e-6), max=1.0)
+        # the scalars as the kernel receives them, each rounded to fp32 once: a group's rows expanded to
+        # per-element vectors, or 0-dim values for the whole buffer
         if groups is not None:
-            # the formulas below with per-element vectors expanded from the rows in place of the scalars
             neg_lr, wd, lr_v, decay = (groups.expand(c).view_as(p) for c in range(4))
-            moves = lr_v != 0  # lr 0: the state advances, p only takes its decay (AdamW's step is 0 / -0 at v = 0)
-            if adam:
-                b1, b2 = betas
-                tf = t.to(torch.float32)
-                pd = p * decay
-                mn = torch.lerp(m, g, 1 - b1)
-                vn = (v * b2).addcmul_(g, g, value=1 - b2)
-                nss = -(lr_v / (1 - b1 ** tf))
-                pn = torch.where(moves, pd.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(eps / nss)), pd)
-            else:
-                g = torch.addcmul(g, p, wd)
-                mn = (m * momentum).add_(g)
-                pn = torch.where(moves, torch.addcmul(p, g.add(mn, alpha=momentum) if nesterov else mn, neg_lr), p)
-        elif adam:
+        else:
+            neg_lr, wd, lr_v, decay = OptimGroups.row_values(lr, [(1.0, weight_decay)])[0].to(p.device)
+        if adam:
             b1, b2 = betas
             tf = t.to(torch.float32)
-            pn = p * (1 - lr * weight_decay)
+            pn = p * decay
             mn = torch.lerp(m, g, 1 - b1)
             vn = (v * b2).addcmul_(g, g, value=1 - b2)
             # p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps), bc_k = 1 - b_k^t, with the step size folded
-            # into the denominator as AdamW(capturable=True) and the kernel spell it
-            nss = -(lr / (1 - b1 ** tf))
-            pn = pn.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(eps / nss))
+            # into the denominator as AdamW(capturable=True) and the kernel spell it; both quotients as the
+            # kernel's reciprocal times the numerator (what float / tensor computes, not tensor / tensor)
+            nss = -((1 - b1 ** tf).reciprocal() * lr_v)
+            step = pn.addcdiv(mn, (vn.sqrt() / ((1 - b2 ** tf).sqrt() * nss)).add_(nss.reciprocal() * eps))
         else:
-            g = g.add(p, alpha=weight_decay)
+            g = torch.addcmul(g, p, wd)
             mn = (m * momentum).add_(g)
-            pn = p.add(g.add(mn, alpha=momentum) if nesterov else mn, alpha=-lr)
+            pn = p
+            step = torch.addcmul(p, g.add(mn, alpha=momentum) if nesterov else mn, neg_lr)
+        # a group at lr 0: the state advances, p only takes its decay (AdamW's step is 0 / -0 at v = 0)
+        pn = torch.where(lr_v != 0, step, pn) if groups is not None else step
         if bf_state:
             m_st.copy_(torch.where(keep, m_st, sr_bf16(mn, r_m.view_as(mn))))
             if adam:

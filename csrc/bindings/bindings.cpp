@@ -18,6 +18,7 @@
 #include <deque>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <set>
 
 #include "../engine/engine.h"
@@ -52,6 +53,25 @@ using CountsArgs = std::tuple<uintptr_t, int64_t, int64_t, int32_t, int64_t, int
 CountsTable counts_table(const CountsArgs& a) {
   const auto [counts, S, step, N, C, kmax] = a;
   return {reinterpret_cast<const int32_t*>(counts), S, step, N, C, kmax};
+}
+
+// Parameter groups as Python passes them: (seg_end, seg_group, rows: device tables; host_seg_end, host_seg_group:
+// their host copies, which the launcher checks; ngroups).  The result points into the tuple's vectors.
+using GroupsArgs =
+    std::tuple<uintptr_t, uintptr_t, uintptr_t, std::vector<int64_t>, std::vector<int32_t>, int32_t>;
+OptimGroups optim_groups(const GroupsArgs& a) {
+  const auto& [seg_end, seg_group, rows, host_seg_end, host_seg_group, ngroups] = a;
+  AKKA_CHECK(!host_seg_end.empty() && host_seg_end.size() == host_seg_group.size(),
+             "count_optim: one group per segment");
+  OptimGroups g;
+  g.seg_end = reinterpret_cast<const int64_t*>(seg_end);
+  g.seg_group = reinterpret_cast<const int32_t*>(seg_group);
+  g.rows = reinterpret_cast<const float*>(rows);
+  g.nseg = int32_t(host_seg_end.size());
+  g.ngroups = ngroups;
+  g.host_seg_end = host_seg_end.data();
+  g.host_seg_group = host_seg_group.data();
+  return g;
 }
 
 struct PySimHub {
@@ -1078,55 +1098,29 @@ PYBIND11_MODULE(_native, m) {
                       reinterpret_cast<void*>(shadow));
   }, py::arg("dst"), py::arg("src"), py::arg("table"), py::arg("dtype"), py::arg("stream"), py::arg("axpy") = false,
      py::arg("alpha") = 0.f, py::arg("shadow") = 0, py::arg("src_dtype") = "");
-  // the hyper-parameters are keyword-only: OptimSpec's fields, with its defaults
+  // the hyper-parameters are keyword-only: OptimSpec's fields, with its defaults (lr and weight_decay are the
+  // groups' business when there are groups)
   m.def("count_optim", [](const std::string& kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow,
                           uintptr_t src, const std::string& src_dtype, const CountsArgs& table, uintptr_t t,
                           uintptr_t sq, uintptr_t stream, bool nt, double lr, double weight_decay, double momentum,
                           bool nesterov, double beta1, double beta2, double eps, double max_norm,
-                          const std::string& state_dtype, uint32_t seed) {
+                          const std::string& state_dtype, uint32_t seed, const std::optional<GroupsArgs>& groups) {
     AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim: kind is 'sgd' or 'adamw'");
     const OptimSpec o{kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD, lr, weight_decay, momentum, nesterov,
                       beta1, beta2, eps, max_norm};
-    launch_count_optim(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom),
-                       reinterpret_cast<void*>(v), parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
-                       reinterpret_cast<const void*>(src), parse_dtype(src_dtype), counts_table(table), o,
-                       reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed, nt);
+    const OptimBuffers b{reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom), reinterpret_cast<void*>(v),
+                         parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
+                         reinterpret_cast<const void*>(src), parse_dtype(src_dtype),
+                         reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed};
+    OptimGroups g;
+    if (groups) g = optim_groups(*groups);
+    launch_count_optim(as_stream(stream), b, counts_table(table), o, groups ? &g : nullptr, nt);
   }, py::arg("kind"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("src"),
      py::arg("src_dtype"), py::arg("table"), py::arg("t"), py::arg("sq"), py::arg("stream") = 0,
-     py::arg("nt") = false, py::kw_only(), py::arg("lr"), py::arg("weight_decay") = 0.0, py::arg("momentum") = 0.0,
-     py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-8,
-     py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("seed") = 0u);
-  // seg_end / seg_group / rows: device tables; host_seg_end / host_seg_group: their host copies (checked here)
-  m.def("count_optim_groups", [](const std::string& kind, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t shadow,
-                                 uintptr_t src, const std::string& src_dtype, const CountsArgs& table, uintptr_t t,
-                                 uintptr_t sq, uintptr_t seg_end, uintptr_t seg_group, uintptr_t rows,
-                                 const std::vector<int64_t>& host_seg_end, const std::vector<int32_t>& host_seg_group,
-                                 int32_t ngroups, uintptr_t stream, double momentum, bool nesterov, double beta1,
-                                 double beta2, double eps, double max_norm, const std::string& state_dtype,
-                                 uint32_t seed) {
-    AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim_groups: kind is 'sgd' or 'adamw'");
-    AKKA_CHECK(!host_seg_end.empty() && host_seg_end.size() == host_seg_group.size(),
-               "count_optim_groups: one group per segment");
-    const OptimSpec o{kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD, 0.0, 0.0, momentum, nesterov,
-                      beta1, beta2, eps, max_norm};
-    OptimGroups g;
-    g.seg_end = reinterpret_cast<const int64_t*>(seg_end);
-    g.seg_group = reinterpret_cast<const int32_t*>(seg_group);
-    g.rows = reinterpret_cast<const float*>(rows);
-    g.nseg = int32_t(host_seg_end.size());
-    g.ngroups = ngroups;
-    g.host_seg_end = host_seg_end.data();
-    g.host_seg_group = host_seg_group.data();
-    launch_count_optim_groups(as_stream(stream), reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom),
-                              reinterpret_cast<void*>(v), parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
-                              reinterpret_cast<const void*>(src), parse_dtype(src_dtype), counts_table(table), o, g,
-                              reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed);
-  }, py::arg("kind"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("src"),
-     py::arg("src_dtype"), py::arg("table"), py::arg("t"), py::arg("sq"), py::arg("seg_end"), py::arg("seg_group"),
-     py::arg("rows"), py::arg("host_seg_end"), py::arg("host_seg_group"), py::arg("ngroups"), py::arg("stream") = 0,
-     py::kw_only(), py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9,
-     py::arg("beta2") = 0.999, py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0,
-     py::arg("state_dtype") = "float32", py::arg("seed") = 0u);
+     py::arg("nt") = false, py::kw_only(), py::arg("lr") = 0.0, py::arg("weight_decay") = 0.0,
+     py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
+     py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("seed") = 0u,
+     py::arg("groups") = py::none());
   m.def("count_sqnorm", [](uintptr_t sq, uintptr_t src, const std::string& src_dtype, const CountsArgs& table,
                            uintptr_t part, uintptr_t ticket, uintptr_t stream) {
     launch_count_sqnorm(as_stream(stream), reinterpret_cast<float*>(sq), reinterpret_cast<const void*>(src),

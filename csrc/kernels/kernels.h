@@ -63,19 +63,27 @@ struct OptimSpec {
   double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;  // AdamW
   double max_norm = 0;                            // used with sq
 };
-void launch_count_optim(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow, const void* src,
-                        DType src_dt, const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq,
-                        uint32_t seed = 0, bool nt = false);
-// The same step with parameter groups and a device-resident learning rate.
-// The flat buffer is cut into `nseg` segments: seg_end (device, int64) holds
-// their ascending exclusive ends, the last one S, seg_group (device, int32)
-// each segment's group in [0, ngroups); host_seg_end / host_seg_group are the
-// host copies the launcher checks.  rows (device, float[ngroups][4], 16-B
-// aligned) = {float(-lr_g), float(wd_g), float(lr_g), float(1 - lr_g * wd_g)}
-// per group, read when the kernel RUNS: rewriting them between the replays of a
-// captured step changes its schedule.  o.lr and o.weight_decay are not used;
-// momentum, nesterov, betas, eps and max_norm stay launch arguments.  A group
-// whose lr is 0 advances m and v and leaves p (times its decay of 1) in place.
+// With `groups` the flat buffer is cut into `nseg` segments with one group's
+// learning rate and weight decay each: seg_end (device, int64) holds their
+// ascending exclusive ends, the last one S, seg_group (device, int32) each
+// segment's group in [0, ngroups); host_seg_end / host_seg_group are the host
+// copies the launcher checks.  rows (device, float[ngroups][4], 16-B aligned) =
+// {float(-lr_g), float(wd_g), float(lr_g), float(1 - lr_g * wd_g)} per group,
+// read when the kernel RUNS: rewriting them between the replays of a captured
+// step changes its schedule.  o.lr and o.weight_decay are then not used, and nt
+// is refused.  A group whose lr is 0 advances m and v and leaves p (times its
+// decay of 1) in place.
+struct OptimBuffers {
+  float* p = nullptr;
+  void *m = nullptr, *v = nullptr;
+  DType state_dt = DType::F32;
+  void* shadow = nullptr;
+  const void* src = nullptr;
+  DType src_dt = DType::F32;
+  const int32_t* t = nullptr;
+  const float* sq = nullptr;
+  uint32_t seed = 0;
+};
 struct OptimGroups {
   const int64_t* seg_end = nullptr;
   const int32_t* seg_group = nullptr;
@@ -84,9 +92,8 @@ struct OptimGroups {
   const int64_t* host_seg_end = nullptr;
   const int32_t* host_seg_group = nullptr;
 };
-void launch_count_optim_groups(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow,
-                               const void* src, DType src_dt, const CountsTable& ct, const OptimSpec& o,
-                               const OptimGroups& g, const int32_t* t, const float* sq, uint32_t seed = 0);
+void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
+                        const OptimGroups* groups = nullptr, bool nt = false);
 // sq[0] = sum over the elements whose count is > 0 of (src / count)^2.  part:
 // fp32 [count_sqnorm_partials()] workspace; ticket: one uint32 zeroed once
 // (each launch leaves it zero again).  Deterministic for a given shape.

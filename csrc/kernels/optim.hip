@@ -40,10 +40,9 @@
 // element off SGD and 8 B off AdamW, and the time follows the bytes
 // (profiles/r10/bf16_state/README.md).
 //
-// count_optim_groups: the same pass with per-group weight decay and learning
-// rate, both read from a small device table when the kernel runs (below, at
-// the kernel).  Both kernels share update_range / update_one and the
-// coefficient code; numbers in profiles/r09/param_groups/README.md.
+// With a group table the same kernel takes each group's weight decay and
+// learning rate from a small device table when it runs (below, at the kernel);
+// numbers in profiles/r09/param_groups/README.md.
 //
 // count_sqnorm: sq[0] = sum over count > 0 of (sum / count)^2, the squared
 // global norm of the mean gradient the clip needs.  fp32 partials per thread,
@@ -75,7 +74,7 @@ struct OptimK {
 struct Coef {
   float clip;    // gradient scale
   float d1, d2;  // AdamW: p += m / (sqrt(v) / d1 + d2)
-  bool move;     // count_optim_groups: false for a group whose learning rate is 0
+  bool move;     // with a group table: false for a group whose learning rate is 0
 };
 
 // The part of them that does not depend on the learning rate: once per kernel.
@@ -99,7 +98,7 @@ __device__ __forceinline__ StepCoef step_coefficients(const OptimK& k, const int
   return c;
 }
 
-// The part that does: once per kernel (count_optim) or per group sub-range (count_optim_groups).
+// The part that does: once per kernel, or per group sub-range with a group table.
 template <bool ADAM>
 __device__ __forceinline__ Coef lr_coefficients(const StepCoef& sc, float lr, float eps) {
 #pragma clang fp contract(off)
@@ -299,50 +298,46 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restri
   }
 }
 
-template <typename TS, typename TM, bool ADAM, bool SHADOW, bool NT>
+// The end of the kernel arguments: the rounding seed alone, or the group table
+// in front of it.  The seed is the last member in both, so the arguments keep
+// one layout whichever tail the kernel takes.
+struct PlainTail {
+  uint32_t seed;
+};
+// The flat buffer is cut into segments (seg_end: ascending exclusive ends, the
+// last one S; seg_group: each segment's group) and rows[g] = {neg_lr, wd, lr,
+// decay} holds group g's host-rounded scalars in DEVICE memory, read when the
+// kernel runs: rewriting the rows between the replays of a captured step
+// changes its learning rate.
+struct GroupTail {
+  const int64_t* __restrict__ seg_end;
+  const int32_t* __restrict__ seg_group;
+  const float4* __restrict__ rows;
+  int32_t nseg, G;
+  uint32_t seed;
+};
+
+// Region walk spelled out here as in count_mean, on purpose (the comment at
+// count_mean_kernel, counts.hip).  Tail = PlainTail: one set of scalars for the
+// whole buffer, from k.  Tail = GroupTail: a region is walked by its
+// intersections with the segments, each processed as the plain pass processes a
+// region, with its group's row.  Everything that picks the segment and the row
+// is wave-uniform (scalar loads, scalar branches).
+template <typename TS, typename TM, bool ADAM, bool SHADOW, bool NT, typename Tail>
 __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__ p, TM* __restrict__ m,
                                                              TM* __restrict__ v, bf16_t* __restrict__ shadow,
                                                              const TS* __restrict__ src,
                                                              const int32_t* __restrict__ counts, int64_t S,
                                                              int64_t step, int32_t N, int64_t C, int32_t kmax,
                                                              OptimK k, const int32_t* __restrict__ t,
-                                                             const float* __restrict__ sq, uint32_t seed) {
-  const Coef c = lr_coefficients<ADAM>(step_coefficients<ADAM>(k, t, sq), k.lr, k.eps);
-  uint32_t key = 0;
-  if constexpr (Elt<TM>::kPerVec == 8) key = sr_key(seed, t);
-  const int64_t nregions = int64_t(N) * kmax;
-  for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
-    const int32_t j = int32_t(reg / kmax);
-    const int64_t kk = reg - int64_t(j) * kmax;
-    const int64_t bs = j * step < S ? j * step : S;
-    const int64_t be = j >= N - 1 ? S : ((j + 1) * step < S ? (j + 1) * step : S);
-    const int64_t s = bs + kk * C;
-    if (s >= be) continue;
-    const int64_t e = s + C < be ? s + C : be;
-    const int32_t cnt = counts[reg];
-    if (cnt <= 0) continue;  // missing: nothing of this region is loaded or stored
-    update_range<TS, TM, ADAM, SHADOW, NT>(p, m, v, shadow, src, s, e, float(cnt), k, c, key);
-  }
-}
-
-// count_optim with parameter groups.  The flat buffer is cut into segments
-// (seg_end: ascending exclusive ends, the last one S; seg_group: each
-// segment's group) and rows[g] = {neg_lr, wd, lr, decay} holds group g's
-// host-rounded scalars in DEVICE memory, read when the kernel runs: rewriting
-// the rows between the replays of a captured step changes its learning rate.
-// A region is walked by its intersections with the segments, each processed as
-// count_optim processes a region, with its group's row.  Everything that picks
-// the segment and the row is wave-uniform (scalar loads, scalar branches).
-template <typename TS, typename TM, bool ADAM, bool SHADOW>
-__global__ __launch_bounds__(kBlock) void count_optim_groups_kernel(
-    float* __restrict__ p, TM* __restrict__ m, TM* __restrict__ v, bf16_t* __restrict__ shadow,
-    const TS* __restrict__ src, const int32_t* __restrict__ counts, int64_t S, int64_t step, int32_t N, int64_t C,
-    int32_t kmax, OptimK k, const int32_t* __restrict__ t, const float* __restrict__ sq,
-    const int64_t* __restrict__ seg_end, const int32_t* __restrict__ seg_group, const float4* __restrict__ rows,
-    int32_t nseg, int32_t G, uint32_t seed) {
+                                                             const float* __restrict__ sq, Tail tail) {
+  constexpr bool GROUPS = std::is_same_v<Tail, GroupTail>;
+  static_assert(!(GROUPS && NT), "the grouped pass has no nontemporal variant");
   const StepCoef sc = step_coefficients<ADAM>(k, t, sq);
+  Coef c{};
+  if constexpr (!GROUPS) c = lr_coefficients<ADAM>(sc, k.lr, k.eps);
   uint32_t key = 0;
-  if constexpr (Elt<TM>::kPerVec == 8) key = sr_key(seed, t);
+  if constexpr (Elt<TM>::kPerVec == 8) key = sr_key(tail.seed, t);
   const int64_t nregions = int64_t(N) * kmax;
   for (int64_t reg = blockIdx.x; reg < nregions; reg += gridDim.x) {
     const int32_t j = int32_t(reg / kmax);
@@ -355,30 +350,34 @@ __global__ __launch_bounds__(kBlock) void count_optim_groups_kernel(
     const int32_t cnt = counts[reg];
     if (cnt <= 0) continue;  // missing: nothing of this region is loaded or stored
     const float fv = float(cnt);
-    // the first segment whose end is past s (there is one: the last segment ends at S > s)
-    int32_t lo = 0, hi = nseg - 1;
-    while (lo < hi) {
-      const int32_t mid = (lo + hi) >> 1;
-      if (seg_end[mid] > s) hi = mid;
-      else lo = mid + 1;
-    }
-    int64_t cur = s;
-    for (int32_t si = lo; cur < e && si < nseg; ++si) {
-      const int64_t se = seg_end[si];
-      const int64_t ee = se < e ? se : e;
-      if (ee <= cur) continue;
-      const uint32_t g = uint32_t(seg_group[si]);
-      if (g < uint32_t(G)) {  // the launcher checked the host copy; a row is never read out of bounds
-        const float4 r = rows[g];
-        OptimK kg = k;
-        kg.neg_lr = r.x;
-        kg.wd = r.y;
-        kg.lr = r.z;
-        kg.decay = r.w;
-        update_range<TS, TM, ADAM, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
-                                                        lr_coefficients<ADAM>(sc, r.z, k.eps), key);
+    if constexpr (GROUPS) {
+      // the first segment whose end is past s (there is one: the last segment ends at S > s)
+      int32_t lo = 0, hi = tail.nseg - 1;
+      while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (tail.seg_end[mid] > s) hi = mid;
+        else lo = mid + 1;
       }
-      cur = ee;
+      int64_t cur = s;
+      for (int32_t si = lo; cur < e && si < tail.nseg; ++si) {
+        const int64_t se = tail.seg_end[si];
+        const int64_t ee = se < e ? se : e;
+        if (ee <= cur) continue;
+        const uint32_t g = uint32_t(tail.seg_group[si]);
+        if (g < uint32_t(tail.G)) {  // the launcher checked the host copy; a row is never read out of bounds
+          const float4 r = tail.rows[g];
+          OptimK kg = k;
+          kg.neg_lr = r.x;
+          kg.wd = r.y;
+          kg.lr = r.z;
+          kg.decay = r.w;
+          update_range<TS, TM, ADAM, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
+                                                          lr_coefficients<ADAM>(sc, r.z, k.eps), key);
+        }
+        cur = ee;
+      }
+    } else {
+      update_range<TS, TM, ADAM, SHADOW, NT>(p, m, v, shadow, src, s, e, fv, k, c, key);
     }
   }
 }
@@ -477,20 +476,56 @@ __global__ __launch_bounds__(kBlock) void count_sqnorm_kernel(float* __restrict_
 
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// Run-time values as template arguments, in the style of dispatch_int:
+// f(Elem<float>{}) or f(Elem<bf16_t>{}) for a dtype, f(std::bool_constant<b>{}) for a flag.
+template <typename T>
+struct Elem {
+  using type = T;
+};
+template <typename F>
+void with_elem(DType dt, F&& f) {
+  if (dt == DType::BF16) f(Elem<bf16_t>{});
+  else f(Elem<float>{});
+}
+template <typename F>
+void with_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 }  // namespace
 
-void launch_count_optim(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow, const void* src,
-                        DType src_dt, const CountsTable& ct, const OptimSpec& o, const int32_t* t, const float* sq,
-                        uint32_t seed, bool nt) {
+void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
+                        const OptimGroups* groups, bool nt) {
   if (ct.S <= 0) return;
   const bool adam = o.kind == OptimKind::AdamW;
-  const bool bf_state = state_dt == DType::BF16;
+  const bool bf_state = b.state_dt == DType::BF16;
   AKKA_CHECK(!(bf_state && nt), "count_optim: no nontemporal variant with bfloat16 state");
+  AKKA_CHECK(!(groups && nt), "count_optim: no nontemporal variant with parameter groups");
   // bf16 state reads the step for its rounding key, whatever the kind
-  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)) && (!bf_state || t), "count_optim: null buffer");
-  AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
+  AKKA_CHECK(b.p && b.m && b.src && ct.counts && (!adam || (b.v && b.t)) && (!bf_state || b.t),
+             "count_optim: null buffer");
+  AKKA_CHECK(aligned16(b.p) && aligned16(b.m) && aligned16(b.v) && aligned16(b.shadow) && aligned16(b.src),
              "count_optim: buffers must be 16-B aligned");
   ct.check("count_optim");
+  if (groups) {
+    const OptimGroups& g = *groups;
+    AKKA_CHECK(g.nseg > 0 && g.ngroups > 0 && g.seg_end && g.seg_group && g.rows && g.host_seg_end &&
+                   g.host_seg_group,
+               "count_optim: no segments, no groups or a null table");
+    AKKA_CHECK(aligned16(g.rows) && (reinterpret_cast<uintptr_t>(g.seg_end) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(g.seg_group) & 3) == 0,
+               "count_optim: the rows must be 16-B aligned, the segment tables naturally");
+    int64_t prev = 0;
+    for (int32_t i = 0; i < g.nseg; ++i) {
+      AKKA_CHECK(g.host_seg_end[i] > prev, "count_optim: segment ends must be positive and ascending");
+      AKKA_CHECK(g.host_seg_group[i] >= 0 && g.host_seg_group[i] < g.ngroups,
+                 "count_optim: a segment's group is outside [0, groups)");
+      prev = g.host_seg_end[i];
+    }
+    AKKA_CHECK(prev == ct.S, "count_optim: the last segment must end at the buffer's size");
+  }
+  // with groups the learning rate and the decay come from the rows (o's are 0 then)
   OptimK k{};
   k.neg_lr = float(-o.lr);
   k.wd = float(o.weight_decay);
@@ -504,99 +539,32 @@ void launch_count_optim(hipStream_t s, float* p, void* m, void* v, DType state_d
   k.w2 = float(1.0 - o.beta2);
   k.eps = float(o.eps);
   k.max_norm = float(o.max_norm);
-  const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
-  auto* h = static_cast<bf16_t*>(shadow);
-#define AKKA_OPT(TS, TM, AD, SH, NTV)                                                                           \
-  hipLaunchKernelGGL((count_optim_kernel<TS, TM, AD, SH, NTV>), dim3(grid, split), dim3(kBlock), 0, s, p,       \
-                     static_cast<TM*>(m), static_cast<TM*>(v), h, static_cast<const TS*>(src), ct.counts, ct.S, \
-                     ct.step, ct.N, ct.C, ct.kmax, k, t, sq, seed)
-#define AKKA_OPT_NT(TS, AD, SH)                          \
-  do {                                                   \
-    if (bf_state) AKKA_OPT(TS, bf16_t, AD, SH, false);   \
-    else if (nt) AKKA_OPT(TS, float, AD, SH, true);      \
-    else AKKA_OPT(TS, float, AD, SH, false);             \
-  } while (0)
-#define AKKA_OPT_SH(TS, AD)                \
-  do {                                     \
-    if (shadow) AKKA_OPT_NT(TS, AD, true); \
-    else AKKA_OPT_NT(TS, AD, false);       \
-  } while (0)
-  if (src_dt == DType::BF16) {
-    if (adam) AKKA_OPT_SH(bf16_t, true);
-    else AKKA_OPT_SH(bf16_t, false);
-  } else {
-    if (adam) AKKA_OPT_SH(float, true);
-    else AKKA_OPT_SH(float, false);
-  }
-#undef AKKA_OPT_SH
-#undef AKKA_OPT_NT
-#undef AKKA_OPT
+  const RegionGrid rg = region_grid(ct.regions(), ct.S, kMaxGrid);
+  with_elem(b.src_dt, [&](auto ts) {
+    with_flag(adam, [&](auto ad) {
+      with_flag(b.shadow != nullptr, [&](auto sh) {
+        auto launch = [&](auto tm, auto ntv, auto tail) {
+          using TS = typename decltype(ts)::type;
+          using TM = typename decltype(tm)::type;
+          hipLaunchKernelGGL((count_optim_kernel<TS, TM, decltype(ad)::value, decltype(sh)::value,
+                                                 decltype(ntv)::value, decltype(tail)>),
+                             dim3(rg.grid, rg.split), dim3(kBlock), 0, s, b.p, static_cast<TM*>(b.m),
+                             static_cast<TM*>(b.v), static_cast<bf16_t*>(b.shadow), static_cast<const TS*>(b.src),
+                             ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, tail);
+        };
+        // nontemporal accesses: fp32 state without groups only (checked above)
+        if (nt) return launch(Elem<float>{}, std::true_type{}, PlainTail{b.seed});
+        with_elem(b.state_dt, [&](auto tm) {
+          if (groups)
+            launch(tm, std::false_type{},
+                   GroupTail{groups->seg_end, groups->seg_group, reinterpret_cast<const float4*>(groups->rows),
+                             groups->nseg, groups->ngroups, b.seed});
+          else launch(tm, std::false_type{}, PlainTail{b.seed});
+        });
+      });
+    });
+  });
   check_launch("count_optim");
-}
-
-void launch_count_optim_groups(hipStream_t s, float* p, void* m, void* v, DType state_dt, void* shadow,
-                               const void* src, DType src_dt, const CountsTable& ct, const OptimSpec& o,
-                               const OptimGroups& g, const int32_t* t, const float* sq, uint32_t seed) {
-  if (ct.S <= 0) return;
-  const bool adam = o.kind == OptimKind::AdamW;
-  const bool bf_state = state_dt == DType::BF16;
-  AKKA_CHECK(p && m && src && ct.counts && (!adam || (v && t)) && (!bf_state || t),
-             "count_optim_groups: null buffer");
-  AKKA_CHECK(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(shadow) && aligned16(src),
-             "count_optim_groups: buffers must be 16-B aligned");
-  ct.check("count_optim_groups");
-  AKKA_CHECK(g.nseg > 0 && g.ngroups > 0 && g.seg_end && g.seg_group && g.rows && g.host_seg_end && g.host_seg_group,
-             "count_optim_groups: no segments, no groups or a null table");
-  AKKA_CHECK(aligned16(g.rows) && (reinterpret_cast<uintptr_t>(g.seg_end) & 7) == 0 &&
-                 (reinterpret_cast<uintptr_t>(g.seg_group) & 3) == 0,
-             "count_optim_groups: the rows must be 16-B aligned, the segment tables naturally");
-  int64_t prev = 0;
-  for (int32_t i = 0; i < g.nseg; ++i) {
-    AKKA_CHECK(g.host_seg_end[i] > prev, "count_optim_groups: segment ends must be positive and ascending");
-    AKKA_CHECK(g.host_seg_group[i] >= 0 && g.host_seg_group[i] < g.ngroups,
-               "count_optim_groups: a segment's group is outside [0, groups)");
-    prev = g.host_seg_end[i];
-  }
-  AKKA_CHECK(prev == ct.S, "count_optim_groups: the last segment must end at the buffer's size");
-  // the learning rate and the decay come from the rows; everything else is per optimizer
-  OptimK k{};
-  k.mu = float(o.momentum);
-  k.nesterov = o.nesterov ? 1 : 0;
-  k.b1 = float(o.beta1);
-  k.w1 = float(1.0 - o.beta1);
-  k.b2 = float(o.beta2);
-  k.w2 = float(1.0 - o.beta2);
-  k.eps = float(o.eps);
-  k.max_norm = float(o.max_norm);
-  const auto [grid, split] = region_grid(ct.regions(), ct.S, kMaxGrid);
-  auto* h = static_cast<bf16_t*>(shadow);
-  const auto* rows = reinterpret_cast<const float4*>(g.rows);
-#define AKKA_OPTG(TS, TM, AD, SH)                                                                               \
-  hipLaunchKernelGGL((count_optim_groups_kernel<TS, TM, AD, SH>), dim3(grid, split), dim3(kBlock), 0, s, p,     \
-                     static_cast<TM*>(m), static_cast<TM*>(v), h, static_cast<const TS*>(src), ct.counts, ct.S, \
-                     ct.step, ct.N, ct.C, ct.kmax, k, t, sq, g.seg_end, g.seg_group, rows, g.nseg, g.ngroups,   \
-                     seed)
-#define AKKA_OPTG_TM(TS, AD, SH)                \
-  do {                                          \
-    if (bf_state) AKKA_OPTG(TS, bf16_t, AD, SH); \
-    else AKKA_OPTG(TS, float, AD, SH);          \
-  } while (0)
-#define AKKA_OPTG_SH(TS, AD)               \
-  do {                                     \
-    if (shadow) AKKA_OPTG_TM(TS, AD, true); \
-    else AKKA_OPTG_TM(TS, AD, false);      \
-  } while (0)
-  if (src_dt == DType::BF16) {
-    if (adam) AKKA_OPTG_SH(bf16_t, true);
-    else AKKA_OPTG_SH(bf16_t, false);
-  } else {
-    if (adam) AKKA_OPTG_SH(float, true);
-    else AKKA_OPTG_SH(float, false);
-  }
-#undef AKKA_OPTG_SH
-#undef AKKA_OPTG_TM
-#undef AKKA_OPTG
-  check_launch("count_optim_groups");
 }
 
 int32_t count_sqnorm_partials() { return kMaxGrid; }

@@ -4,8 +4,8 @@
 rounding bits across steps and seeds, non-finite values, and the optimizers'
 interface.
 
-``_mix`` / ``_bits`` / ``_sr`` below are this file's own copy of that
-definition (numpy, uint32 arithmetic that wraps), written from the
+``_bits`` / ``_sr`` are the tests' own copy of that definition
+(``optim_cases.py``: numpy, uint32 arithmetic that wraps), written from the
 documentation; nothing of it is imported from the package."""
 import numpy as np
 import pytest
@@ -13,48 +13,10 @@ import torch
 
 from akka_allreduce_amd.data import AllReduceOutput, Geometry, OptimGroups
 from akka_allreduce_amd.parallel import FusedAdamW, FusedSGD
-from akka_allreduce_amd.parallel.dp import GradientBucket
+from optim_cases import BF, H_SENTINEL, HYPER, _bits, _bucket, _same_bits, _sr
 
-BF = torch.bfloat16
-M_SENTINEL, V_SENTINEL, H_SENTINEL = 123.0, 77.5, -3.5  # bf16-representable
+M_SENTINEL, V_SENTINEL = 123.0, 77.5  # bf16-representable
 SHAPES = [(1, 1, 1), (7, 3, 2), (1003, 4, 67)]
-HYPER = {
-    "sgd": dict(lr=0.05, momentum=0.9, nesterov=False, weight_decay=1e-2),
-    "nesterov": dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-2),
-    "adamw": dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01),
-}
-
-
-def _mix(x):
-    x = x ^ (x >> np.uint32(16))
-    x = x * np.uint32(0x7FEB352D)
-    x = x ^ (x >> np.uint32(15))
-    x = x * np.uint32(0x846CA68B)
-    return x ^ (x >> np.uint32(16))
-
-
-def _bits(n, t, seed):
-    """(r_m, r_v) of the elements 0 .. n-1 at step t."""
-    key = _mix(np.array([seed], np.uint32) ^ _mix(np.array([t], np.uint32)))
-    i = np.arange(n, dtype=np.uint64)
-    lo, hi = (i & np.uint64(0xFFFFFFFF)).astype(np.uint32), (i >> np.uint64(32)).astype(np.uint32)
-    h = _mix(lo ^ (hi * np.uint32(0x9E3779B9)) ^ key)
-    return h & np.uint32(0xFFFF), h >> np.uint32(16)
-
-
-def _sr(x, r):
-    """fp32 tensor -> bf16 tensor with the 16-bit r: the upper half of bits + r where x is finite, else the cast."""
-    b = x.detach().contiguous().numpy().view(np.uint32)
-    up = ((b.astype(np.uint64) + np.asarray(r).astype(np.uint64)) >> np.uint64(16)).astype(np.uint16)
-    cast = x.detach().to(BF).contiguous().view(torch.int16).numpy().view(np.uint16)
-    out = np.where((b & np.uint32(0x7F800000)) != np.uint32(0x7F800000), up, cast)
-    return torch.from_numpy(out.view(np.int16).copy()).view(BF)
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.int16 if a.dtype == BF else torch.int32),
-                                              b.contiguous().view(torch.int16 if b.dtype == BF else torch.int32))
-
 
 def _inputs(S, N, C, src):
     geo = Geometry(S, N, C)
@@ -233,11 +195,6 @@ class _OneContributor:
 
     def __call__(self, t, out=None):
         return AllReduceOutput(t.clone(), counts_per_chunk=self.counts, geometry=self.geometry)
-
-
-def _bucket(sizes=(640, 60, 300, 3)):
-    torch.manual_seed(0)
-    return GradientBucket([torch.nn.Parameter(torch.randn(n)) for n in sizes], flatten_params=True)
 
 
 def _steps(b, opt, ar, which):

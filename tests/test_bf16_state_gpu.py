@@ -1,12 +1,12 @@
 """bf16 moments with stochastic rounding on the GPU (``optim.hip``, the
-``bf16_t`` state instantiations of ``count_optim`` / ``count_optim_groups``).
+``bf16_t`` state instantiations of ``count_optim``, with and without a group table).
 
 The reference of one step is the fp32-state kernel run from the widened copies
 of the same bf16 state: ``p`` and the shadow must be its ``p`` and shadow bit
 for bit, and ``m`` / ``v`` its ``m'`` / ``v'`` rounded by ``_sr`` with the bits
-of ``_bits`` -- this file's own numpy copy of the definition at the top of the
-bf16 code in ``csrc/kernels/optim.hip``, written from the documentation and
-not imported from the package."""
+of ``_bits`` -- the tests' own numpy copy (``optim_cases.py``) of the definition
+at the top of the bf16 code in ``csrc/kernels/optim.hip``, written from the
+documentation and not imported from the package."""
 import functools
 import math
 
@@ -14,59 +14,18 @@ import numpy as np
 import pytest
 import torch
 
+import optim_cases
 from akka_allreduce_amd.data import AllReduceOutput, Geometry, OptimGroups, sqnorm_workspace
+from optim_cases import BF, H_SENTINEL, HYPER, _bits, _dev, _kernel_state, _mlp_run, _same_bits, _sr
 
 pytestmark = pytest.mark.gpu
 
-BF = torch.bfloat16
 # one element; regions shorter than a unit; unaligned regions, no multiple of 8; few regions, so that several
 # workgroups share one (gridDim.y > 1) and run the unrolled loop and its remainder
 SHAPES = [(1, 1, 1), (7, 3, 2), (1003, 4, 67), (300_001, 2, 150_000)]
-HYPER = {
-    "sgd": dict(lr=0.05, momentum=0.9, nesterov=False, weight_decay=1e-2),
-    "nesterov": dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-2),
-    "adamw": dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01),
-}
-M_SENTINEL, V_SENTINEL, H_SENTINEL = 123.0, 77.5, -3.5  # bf16-representable
+M_SENTINEL, V_SENTINEL = 123.0, 77.5  # bf16-representable
 SEED = 5
-
-
-def _dev():
-    return torch.device("cuda", 0)
-
-
-def _mix(x):
-    x = x ^ (x >> np.uint32(16))
-    x = x * np.uint32(0x7FEB352D)
-    x = x ^ (x >> np.uint32(15))
-    x = x * np.uint32(0x846CA68B)
-    return x ^ (x >> np.uint32(16))
-
-
-@functools.lru_cache(maxsize=16)
-def _bits(n, t, seed):
-    """(r_m, r_v) of the elements 0 .. n-1 at step t."""
-    key = _mix(np.array([seed], np.uint32) ^ _mix(np.array([t], np.uint32)))
-    i = np.arange(n, dtype=np.uint64)
-    lo, hi = (i & np.uint64(0xFFFFFFFF)).astype(np.uint32), (i >> np.uint64(32)).astype(np.uint32)
-    h = _mix(lo ^ (hi * np.uint32(0x9E3779B9)) ^ key)
-    return h & np.uint32(0xFFFF), h >> np.uint32(16)
-
-
-def _sr(x, r):
-    """fp32 tensor -> bf16 tensor (on the CPU) with the 16-bit r."""
-    x = x.detach().cpu().contiguous()
-    b = x.numpy().view(np.uint32)
-    up = ((b.astype(np.uint64) + np.asarray(r).astype(np.uint64)) >> np.uint64(16)).astype(np.uint16)
-    cast = x.to(BF).contiguous().view(torch.int16).numpy().view(np.uint16)
-    out = np.where((b & np.uint32(0x7F800000)) != np.uint32(0x7F800000), up, cast)
-    return torch.from_numpy(out.view(np.int16).copy()).view(BF)
-
-
-def _same_bits(a, b):
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    it = torch.int16 if a.dtype == BF else torch.int32
-    return a.dtype == b.dtype and torch.equal(a.view(it), b.view(it))
+_step = functools.partial(optim_cases._step, seed=SEED)
 
 
 @functools.lru_cache(maxsize=2)
@@ -94,31 +53,11 @@ def _inputs(S, N, C, src):
                 v0=v0.to(dev), max_norm=0.1 * math.sqrt(S))
 
 
-def _state(inp, dtype=BF):
-    p, m, v = inp["p0"].clone(), inp["m0"].to(dtype), inp["v0"].to(dtype)
-    if dtype == BF:
-        m, v = m.clone(), v.clone()
-    t = torch.zeros(1, dtype=torch.int32, device=p.device)
-    sh = torch.full_like(p, H_SENTINEL, dtype=BF)
-    return [p, m, v, t, sh]
-
-
-def _step(inp, kind, state, i, ws=None, groups=None, geo=None, pc=None, seed=SEED):
-    p, m, v, t, sh = state
-    h = dict(HYPER[kind])
-    lr = h.pop("lr")
-    out = AllReduceOutput(inp["sums"][i % 3], counts_per_chunk=inp["pc"] if pc is None else pc,
-                          geometry=inp["geo"] if geo is None else geo)
-    t.add_(1)
-    out.optim_step_("adamw" if kind == "adamw" else "sgd", p, m, v if kind == "adamw" else None, t, lr, shadow=sh,
-                    max_norm=inp["max_norm"] if ws is not None else None, norm_ws=ws, groups=groups, seed=seed, **h)
-
-
 def _check_steps(inp, kind, S, ws_pair=(None, None), groups=None):
     """Three steps on the evolving bf16 state, each against the fp32-state kernel from the widened state."""
     adam = kind == "adamw"
     missing = inp["missing"]
-    st = _state(inp)
+    st = _kernel_state(inp)
     p, m, v, t, sh = st
     for i in range(3):
         ref = [p.clone(), m.float(), v.float(), t.clone(), sh.clone()]
@@ -169,7 +108,7 @@ def _rows(groups, kind, scales_and_decays):
 @pytest.mark.parametrize("S,N,C", [(1003, 4, 67), (300_001, 2, 150_000)])
 def test_one_group_is_the_plain_pass(S, N, C, kind):
     inp = _inputs(S, N, C, "fp32")
-    plain, grouped = _state(inp), _state(inp)
+    plain, grouped = _kernel_state(inp), _kernel_state(inp)
     groups = _rows(OptimGroups([S], [0], 1, _dev()), kind, [(1.0, HYPER[kind]["weight_decay"])])
     for i in range(3):
         _step(inp, kind, plain, i)
@@ -206,7 +145,7 @@ def test_the_result_does_not_depend_on_the_geometry(kind):
     for N, C in ((1, 1003), (4, 67)):
         geo = Geometry(S, N, C)
         pc = torch.ones((N, geo.kmax), dtype=torch.int32, device=_dev())
-        st = _state(inp)
+        st = _kernel_state(inp)
         for i in range(3):
             _step(inp, kind, st, i, geo=geo, pc=pc)
         torch.cuda.synchronize()
@@ -223,11 +162,11 @@ def test_graph_replay_of_the_bf16_state_pass(src):
     S, N, C = 300_001, 2, 150_000
     inp = _inputs(S, N, C, src)
     dev = _dev()
-    eager = _state(inp)
+    eager = _kernel_state(inp)
     ws_e = sqnorm_workspace(dev)
     for _ in range(3):
         _step(inp, "adamw", eager, 0, ws_e)
-    graphed = _state(inp)
+    graphed = _kernel_state(inp)
     ws_g = sqnorm_workspace(dev)
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))
@@ -296,47 +235,14 @@ def test_non_finite_gradients_reach_m_as_they_are_and_nt_is_refused():
     assert not bool(torch.isnan(f[3:]).any()) and bool((f[7:].abs() <= 2e-40).all())
 
 
-def _mlp_run(graphed, wire, steps=5):
-    from akka_allreduce_amd.models.mlp import MLP, GraphedDPStep, dp_sgd_step, synthetic_batch
-    from akka_allreduce_amd.parallel import FusedAdamW, ThresholdAllreduce
-    from akka_allreduce_amd.parallel.dp import GradientBucket
-
-    dev = _dev()
-    gen = torch.Generator(device=dev).manual_seed(5)
-    batches = [synthetic_batch(32, 64, 10, device=dev, generator=gen) for _ in range(steps)]
-    torch.manual_seed(0)
-    model = MLP(64, 128, 10).to(dev)
-    bucket = GradientBucket(list(model.parameters()), flatten_params=True,
-                            wire_dtype=torch.bfloat16 if wire else None)
-    opt = FusedAdamW(bucket, weight_decay=0.01, max_grad_norm=1.0, state_dtype=BF)
-    assert opt.m.dtype == BF and opt.v.dtype == BF
-    ar = ThresholdAllreduce(bucket.numel, max_chunk_size=4096, device=dev,
-                            **({"dtype": torch.bfloat16} if wire else {}))
-    if graphed:
-        step = GraphedDPStep(model, bucket, *batches[0], compute_dtype=torch.bfloat16, optimizer=opt)
-        assert int(opt.t) == 0  # warmup and capture ran forward + backward only
-        losses = [float(step(x, y, 1e-2, ar)) for x, y in batches]
-        keep = opt.m
-        opt.m = torch.zeros_like(keep)
-        with pytest.raises(RuntimeError, match="moved"):
-            step(*batches[0], 1e-2, ar)
-        opt.m = keep
-    else:
-        losses = [dp_sgd_step(model, x, y, 1e-2, ar, bucket, compute_dtype=torch.bfloat16, optimizer=opt)
-                  for x, y in batches]
-    torch.cuda.synchronize()
-    assert int(opt.t) == steps and bucket._shadow_on
-    return losses, bucket.pflat.clone(), bucket.sflat.clone(), opt.m.clone(), opt.v.clone()
-
-
 @pytest.mark.parametrize("wire", [False, True])
 def test_graphed_mlp_step_with_bf16_state_matches_eager(wire):
-    eager = _mlp_run(False, wire)
-    graphed = _mlp_run(True, wire)
-    assert eager[0] == graphed[0], (eager[0], graphed[0])
-    for name, a, b in zip(("pflat", "sflat", "m", "v"), eager[1:], graphed[1:]):
-        assert _same_bits(a, b), name
-        assert bool(torch.isfinite(a.float()).all()), name
-    assert all(math.isfinite(x) for x in graphed[0])
-    assert torch.equal(graphed[2], graphed[1].to(torch.bfloat16))
-    assert float(graphed[4].float().max()) > 0  # v moved
+    eager = _mlp_run(False, wire, state_dtype=BF)
+    graphed = _mlp_run(True, wire, state_dtype=BF)
+    assert eager["losses"] == graphed["losses"], (eager["losses"], graphed["losses"])
+    for name in ("pflat", "sflat", "m", "v"):
+        assert _same_bits(eager[name], graphed[name]), name
+        assert bool(torch.isfinite(eager[name].float()).all()), name
+    assert all(math.isfinite(x) for x in graphed["losses"])
+    assert torch.equal(graphed["sflat"], graphed["pflat"].to(torch.bfloat16))
+    assert float(graphed["v"].float().max()) > 0  # v moved

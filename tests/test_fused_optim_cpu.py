@@ -5,51 +5,19 @@ put back afterwards (a missing chunk leaves parameters and state untouched)."""
 import pytest
 import torch
 
-from akka_allreduce_amd.data import AllReduceOutput, Geometry
+import optim_cases
 from akka_allreduce_amd.parallel import FusedAdamW, FusedSGD
 from akka_allreduce_amd.parallel.dp import GradientBucket
+from optim_cases import StubAllreduce, _close
 
 S, N, C = 1003, 4, 67
 STEPS = 5
 
 
-class StubAllreduce:
-    """A round whose per-chunk counts are given: every contributor of a chunk
-    sent this rank's values, so the sum is ``count * t`` and 0 where the
-    count is 0."""
-
-    def __init__(self, S, N, C, seed=1):
-        self.geometry = Geometry(S, N, C)
-        g = torch.Generator().manual_seed(seed)
-        pc = torch.randint(0, N + 1, (N, self.geometry.kmax), dtype=torch.int32, generator=g)
-        pc[0, 0] = 0      # a missing chunk
-        pc[1, 0] = N - 1  # a partial one
-        pc[2, 1] = N      # a complete one
-        self.counts = pc
-        self.count = self.geometry.expand_counts(pc)
-        self.last = None
-
-    def __call__(self, t, out=None):
-        data = (t.float() * self.count).to(t.dtype)
-        self.last = data
-        return AllReduceOutput(data, counts_per_chunk=self.counts, geometry=self.geometry)
-
-    def mean(self):
-        c = self.count.float()
-        return torch.where(c > 0, self.last.float() / c.clamp(min=1), torch.zeros_like(c))
-
-
 def _bucket(wire):
-    torch.manual_seed(0)
-    ps = [torch.nn.Parameter(torch.randn(n)) for n in (700, 300, 3)]
-    assert sum(p.numel() for p in ps) == S
-    return GradientBucket(ps, flatten_params=True, wire_dtype=torch.bfloat16 if wire else None)
-
-
-def _close(got, want, what):
-    # per step a few fp32 roundings (2**-24) of operands no larger than the largest value
-    torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-6 * float(want.abs().max()) + 1e-12,
-                               msg=lambda m: f"{what}: {m}")
+    b = optim_cases._bucket(wire, sizes=(700, 300, 3))
+    assert b.numel == S
+    return b
 
 
 @pytest.mark.parametrize("wire", [False, True])

@@ -16,7 +16,9 @@ import math
 import pytest
 import torch
 
-from akka_allreduce_amd.data import AllReduceOutput, Geometry, sqnorm_workspace
+from akka_allreduce_amd.data import AllReduceOutput, sqnorm_workspace
+from optim_cases import (H_SENTINEL, HYPER, M_SENTINEL, NGRAD, V_SENTINEL, _dev, _inputs, _kernel_state, _mlp_run,
+                         _step)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,49 +27,6 @@ pytestmark = pytest.mark.gpu
 # and run the unrolled loop and its remainder; many regions with bodies, heads and tails
 SHAPES = [(1, 1, 1), (7, 3, 2), (1003, 4, 67), (300_001, 2, 150_000), (1_000_003, 4, 4099)]
 STEPS = (1, 20)
-NGRAD = 4
-HYPER = {
-    "sgd": dict(lr=0.05, momentum=0.9, nesterov=False, weight_decay=1e-2),
-    "nesterov": dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-2),
-    "adamw": dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01),
-}
-M_SENTINEL, V_SENTINEL, H_SENTINEL = 123.25, 77.5, -3.5
-
-
-def _dev():
-    return torch.device("cuda", 0)
-
-
-@functools.lru_cache(maxsize=2)
-def _inputs(S, N, C, src):
-    """Counts (random in [0, N], one chunk forced to 0 and one to N), NGRAD
-    sums of the source dtype with their fp32 means, and the initial state with
-    sentinels in the count-0 elements."""
-    dev = _dev()
-    geo = Geometry(S, N, C)
-    g = torch.Generator(device="cpu").manual_seed(S * 31 + N)
-    pc = torch.randint(0, N + 1, (N, geo.kmax), dtype=torch.int32, generator=g)
-    pc[0, 0] = 0
-    pc[N - 1, 0] = N
-    count = geo.expand_counts(pc).to(dev)
-    pc = pc.to(dev)
-    missing = count == 0
-    sums, means = [], []
-    for i in range(NGRAD):
-        base = torch.randn(S, generator=g).to(dev)
-        if i == 2:
-            base = base * 1e-2  # a round whose norm is below max_norm: the clip coefficient clamps to 1
-        # count-0 elements keep a non-zero sum: it must not be read
-        s = torch.where(missing, base, base * count).to(torch.bfloat16 if src == "bf16" else torch.float32)
-        sums.append(s)
-        means.append(AllReduceOutput(s, counts_per_chunk=pc, geometry=geo).mean(dtype=torch.float32).clone()
-                     if src == "bf16" else AllReduceOutput(s, counts_per_chunk=pc, geometry=geo).mean().clone())
-    p0 = torch.randn(S, generator=g).to(dev)
-    m0 = torch.where(missing, torch.full_like(p0, M_SENTINEL), torch.zeros_like(p0))
-    v0 = torch.where(missing, torch.full_like(p0, V_SENTINEL), torch.zeros_like(p0))
-    torch.cuda.synchronize()
-    return dict(geo=geo, pc=pc, count=count, missing=missing, sums=sums, means=means, p0=p0, m0=m0, v0=v0,
-                max_norm=0.1 * math.sqrt(S))
 
 
 def _torch_run(kind, inp, dtype, clip):
@@ -108,23 +67,6 @@ def _references(S, N, C, src, kind, clip):
     r = _torch_run(kind, inp, torch.float64, clip), _torch_run(kind, inp, torch.float32, clip)
     torch.cuda.synchronize()
     return r
-
-
-def _kernel_state(inp, shadow):
-    p, m, v = inp["p0"].clone(), inp["m0"].clone(), inp["v0"].clone()
-    t = torch.zeros(1, dtype=torch.int32, device=p.device)
-    sh = torch.full_like(p, H_SENTINEL, dtype=torch.bfloat16) if shadow else None
-    return p, m, v, t, sh
-
-
-def _step(inp, kind, state, i, ws):
-    p, m, v, t, sh = state
-    h = dict(HYPER[kind])
-    lr = h.pop("lr")
-    out = AllReduceOutput(inp["sums"][i % NGRAD], counts_per_chunk=inp["pc"], geometry=inp["geo"])
-    t.add_(1)
-    out.optim_step_("adamw" if kind == "adamw" else "sgd", p, m, v if kind == "adamw" else None, t, lr, shadow=sh,
-                    max_norm=inp["max_norm"] if ws is not None else None, norm_ws=ws, **h)
 
 
 # the topmost parameter varies fastest: both shadow cases share one reference, every case of a shape its inputs
@@ -245,43 +187,11 @@ def test_graph_replay_of_the_adamw_pass(src):
     assert torch.equal(ws_e[:2], ws_g[:2])
 
 
-def _mlp_run(graphed, wire, steps=5):
-    from akka_allreduce_amd.models.mlp import MLP, GraphedDPStep, dp_sgd_step, synthetic_batch
-    from akka_allreduce_amd.parallel import FusedAdamW, ThresholdAllreduce
-    from akka_allreduce_amd.parallel.dp import GradientBucket
-
-    dev = _dev()
-    gen = torch.Generator(device=dev).manual_seed(5)
-    batches = [synthetic_batch(32, 64, 10, device=dev, generator=gen) for _ in range(steps)]
-    torch.manual_seed(0)
-    model = MLP(64, 128, 10).to(dev)
-    bucket = GradientBucket(list(model.parameters()), flatten_params=True,
-                            wire_dtype=torch.bfloat16 if wire else None)
-    opt = FusedAdamW(bucket, weight_decay=0.01, max_grad_norm=1.0)
-    ar = ThresholdAllreduce(bucket.numel, max_chunk_size=4096, device=dev,
-                            **({"dtype": torch.bfloat16} if wire else {}))
-    if graphed:
-        step = GraphedDPStep(model, bucket, *batches[0], compute_dtype=torch.bfloat16, optimizer=opt)
-        assert int(opt.t) == 0  # warmup and capture ran forward + backward only
-        losses = [float(step(x, y, 1e-2, ar)) for x, y in batches]
-        keep = opt.m
-        opt.m = torch.zeros_like(keep)
-        with pytest.raises(RuntimeError, match="moved"):
-            step(*batches[0], 1e-2, ar)
-        opt.m = keep
-    else:
-        losses = [dp_sgd_step(model, x, y, 1e-2, ar, bucket, compute_dtype=torch.bfloat16, optimizer=opt)
-                  for x, y in batches]
-    torch.cuda.synchronize()
-    assert int(opt.t) == steps and bucket._shadow_on
-    return losses, bucket.pflat.clone(), bucket.sflat.clone(), opt.m.clone(), opt.v.clone()
-
-
 @pytest.mark.parametrize("wire", [False, True])
 def test_graphed_mlp_step_with_fused_adamw_matches_eager(wire):
     eager = _mlp_run(False, wire)
     graphed = _mlp_run(True, wire)
-    assert eager[0] == graphed[0], (eager[0], graphed[0])
-    for name, a, b in zip(("pflat", "sflat", "m", "v"), eager[1:], graphed[1:]):
-        assert torch.equal(a, b), name
-    assert torch.equal(graphed[2], graphed[1].to(torch.bfloat16))
+    assert eager["losses"] == graphed["losses"], (eager["losses"], graphed["losses"])
+    for name in ("pflat", "sflat", "m", "v"):
+        assert torch.equal(eager[name], graphed[name]), name
+    assert torch.equal(graphed["sflat"], graphed["pflat"].to(torch.bfloat16))

@@ -3,52 +3,17 @@ FusedAdamW on the CPU: validation, segment merging, the torch expression of
 the grouped pass (``optim_step_(groups=...)``) against torch's optimizers with
 the same ``param_groups``, the zero-lr rule and the ``state_dict`` round trip.
 Bound and method of the torch comparison are ``test_fused_optim_cpu.py``'s."""
+import itertools
+
 import pytest
 import torch
 
-from akka_allreduce_amd.data import AllReduceOutput, Geometry, OptimGroups
+from akka_allreduce_amd.data import AllReduceOutput, Geometry, OptimGroups, sqnorm_workspace
 from akka_allreduce_amd.parallel import FusedAdamW, FusedSGD
-from akka_allreduce_amd.parallel.dp import GradientBucket
+from optim_cases import BF, HYPER, StubAllreduce, _bucket, _close, _same_bits
 
 S, N, C = 1003, 4, 67
-SIZES = (640, 60, 300, 3)  # "weight, bias, weight, bias"
 STEPS = 20
-
-
-class StubAllreduce:
-    """A round whose per-chunk counts are given: the sum is ``count * t``."""
-
-    def __init__(self, S, N, C, seed=1):
-        self.geometry = Geometry(S, N, C)
-        g = torch.Generator().manual_seed(seed)
-        pc = torch.randint(0, N + 1, (N, self.geometry.kmax), dtype=torch.int32, generator=g)
-        pc[0, 0] = 0      # a missing chunk
-        pc[1, 0] = N - 1  # a partial one
-        pc[2, 1] = N      # a complete one
-        self.counts = pc
-        self.count = self.geometry.expand_counts(pc)
-        self.last = None
-
-    def __call__(self, t, out=None):
-        data = (t.float() * self.count).to(t.dtype)
-        self.last = data
-        return AllReduceOutput(data, counts_per_chunk=self.counts, geometry=self.geometry)
-
-    def mean(self):
-        c = self.count.float()
-        return torch.where(c > 0, self.last.float() / c.clamp(min=1), torch.zeros_like(c))
-
-
-def _bucket(wire=False, sizes=SIZES):
-    torch.manual_seed(0)
-    ps = [torch.nn.Parameter(torch.randn(n)) for n in sizes]
-    return GradientBucket(ps, flatten_params=True, wire_dtype=torch.bfloat16 if wire else None)
-
-
-def _close(got, want, what):
-    # per step a few fp32 roundings (2**-24) of operands no larger than the largest value
-    torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-6 * float(want.abs().max()) + 1e-12,
-                               msg=lambda m: f"{what}: {m}")
 
 
 @pytest.mark.parametrize("cls", [FusedSGD, FusedAdamW])
@@ -260,3 +225,43 @@ def test_load_state_dict_takes_the_groups_hyper_parameters_and_rewrites_the_rows
     o2.load_state_dict(d)
     assert o2.param_groups == o.param_groups and torch.equal(o2.groups.rows, o.groups.rows)
     assert float(o2.groups.rows[0, 2]) == 2.0 and float(o2.groups.rows[0, 1]) == 0.25
+
+
+def test_plain_torch_path_is_the_one_group_path_bitwise():
+    """The torch path of ``optim_step_`` has one set of formulas and two ways in: ``lr`` / ``weight_decay`` as
+    0-dim values, or the rows of ``groups`` expanded per element.  With one group over the whole buffer, whose row
+    is made from the same ``lr`` and ``weight_decay``, both give the same bits: fp32 and bf16 sums and state, every
+    kind, with and without the clip, random counts in [0, N] (some chunks missing), at step 7."""
+    t = torch.full((1,), 7, dtype=torch.int32)
+    cases = 0
+    for (S, N, C), src, sdt, kind, clip in itertools.product(
+            [(1000, 3, 64), (4099, 4, 257), (37, 5, 3)], (torch.float32, BF), (torch.float32, BF),
+            ("sgd", "nesterov", "adamw"), (False, True)):
+        geo = Geometry(S, N, C)
+        g = torch.Generator().manual_seed(S * 31 + N)
+        pc = torch.randint(0, N + 1, (N, geo.kmax), dtype=torch.int32, generator=g)
+        count = geo.expand_counts(pc)
+        assert bool((count == 0).any()) and bool((count > 0).any())
+        data = (torch.randn(S, generator=g) * count).to(src)
+        start = [torch.randn(S, generator=g), (0.1 * torch.randn(S, generator=g)).to(sdt),
+                 (0.01 * torch.rand(S, generator=g)).to(sdt), torch.full((S,), -3.5, dtype=BF)]
+        adam = kind == "adamw"
+        h = dict(HYPER[kind])
+        lr, wd = h.pop("lr"), h.pop("weight_decay")
+        groups = OptimGroups([S], [0], 1, "cpu")
+        groups.write_rows(OptimGroups.row_values(lr, [(1.0, wd)]))
+        runs = []
+        for gr in (None, groups):
+            p, m, v, sh = (x.clone() for x in start)
+            out = AllReduceOutput(data, counts_per_chunk=pc, geometry=geo)
+            # with groups lr and weight_decay are not used: 0 is passed
+            out.optim_step_("adamw" if adam else "sgd", p, m, v if adam else None, t, lr if gr is None else 0.0,
+                            weight_decay=wd if gr is None else 0.0, shadow=sh, seed=5,
+                            max_norm=0.1 * S ** 0.5 if clip else None,
+                            norm_ws=sqnorm_workspace("cpu") if clip else None, groups=gr, **h)
+            runs.append((p, m, v, sh))
+        for name, a, b in zip(("p", "m", "v", "shadow"), *runs):
+            assert _same_bits(a, b), (S, src, sdt, kind, clip, name)
+        assert not _same_bits(runs[0][0], start[0]) and not _same_bits(runs[0][1], start[1])
+        cases += 1
+    assert cases == 72

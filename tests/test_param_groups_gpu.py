@@ -1,6 +1,6 @@
-"""The grouped optimizer pass on the GPU (``optim.hip``: ``count_optim_groups``)
-and what is built on it: per-group weight decay and learning rate read from a
-device table when the kernel runs.
+"""The grouped optimizer pass on the GPU (``optim.hip``: ``count_optim`` with a
+group table) and what is built on it: per-group weight decay and learning rate
+read from a device table when the kernel runs.
 
 Numerics as in ``test_fused_optim_gpu.py``: from the same fp32 inputs torch's
 optimizer in float64 is the reference and torch's optimizer in fp32 on the GPU
@@ -17,7 +17,9 @@ import math
 import pytest
 import torch
 
-from akka_allreduce_amd.data import AllReduceOutput, Geometry, OptimGroups, sqnorm_workspace
+from akka_allreduce_amd.data import OptimGroups, sqnorm_workspace
+from optim_cases import (H_SENTINEL, HYPER, M_SENTINEL, NGRAD, V_SENTINEL, _dev, _inputs, _kernel_state, _mlp_run,
+                         _step)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,50 +46,6 @@ assert len(CASES["search"][1]) == 258 and len(set(CASES["search"][1])) == 258
 # groups round-robin over the segments, so neighbours always differ
 GROUP_SCALE, GROUP_WD = (1.0, 0.1, 2.5), (0.01, 0.0, 0.1)
 STEPS = (1, 20)
-NGRAD = 4
-# the hyper-parameters of test_fused_optim_gpu.py
-HYPER = {
-    "sgd": dict(lr=0.05, momentum=0.9, nesterov=False, weight_decay=1e-2),
-    "nesterov": dict(lr=0.05, momentum=0.9, nesterov=True, weight_decay=1e-2),
-    "adamw": dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01),
-}
-M_SENTINEL, V_SENTINEL, H_SENTINEL = 123.25, 77.5, -3.5
-
-
-def _dev():
-    return torch.device("cuda", 0)
-
-
-@functools.lru_cache(maxsize=2)
-def _inputs(S, N, C, src):
-    """Counts (random in [0, N], one chunk forced to 0 and one to N), NGRAD
-    sums of the source dtype with their fp32 means, and the initial state with
-    sentinels in the count-0 elements."""
-    dev = _dev()
-    geo = Geometry(S, N, C)
-    g = torch.Generator(device="cpu").manual_seed(S * 31 + N)
-    pc = torch.randint(0, N + 1, (N, geo.kmax), dtype=torch.int32, generator=g)
-    pc[0, 0] = 0
-    pc[N - 1, 0] = N
-    count = geo.expand_counts(pc).to(dev)
-    pc = pc.to(dev)
-    missing = count == 0
-    sums, means = [], []
-    for i in range(NGRAD):
-        base = torch.randn(S, generator=g).to(dev)
-        if i == 2:
-            base = base * 1e-2  # a round whose norm is below max_norm: the clip coefficient clamps to 1
-        # count-0 elements keep a non-zero sum: it must not be read
-        s = torch.where(missing, base, base * count).to(torch.bfloat16 if src == "bf16" else torch.float32)
-        sums.append(s)
-        out = AllReduceOutput(s, counts_per_chunk=pc, geometry=geo)
-        means.append((out.mean(dtype=torch.float32) if src == "bf16" else out.mean()).clone())
-    p0 = torch.randn(S, generator=g).to(dev)
-    m0 = torch.where(missing, torch.full_like(p0, M_SENTINEL), torch.zeros_like(p0))
-    v0 = torch.where(missing, torch.full_like(p0, V_SENTINEL), torch.zeros_like(p0))
-    torch.cuda.synchronize()
-    return dict(geo=geo, pc=pc, count=count, missing=missing, sums=sums, means=means, p0=p0, m0=m0, v0=v0,
-                max_norm=0.1 * math.sqrt(S))
 
 
 def _groups(ends, lr, scales=GROUP_SCALE, wds=GROUP_WD):
@@ -143,28 +101,6 @@ def _references(case, src, kind, clip):
     r = _torch_run(kind, inp, ends, torch.float64, clip), _torch_run(kind, inp, ends, torch.float32, clip)
     torch.cuda.synchronize()
     return r
-
-
-def _kernel_state(inp, shadow):
-    p, m, v = inp["p0"].clone(), inp["m0"].clone(), inp["v0"].clone()
-    t = torch.zeros(1, dtype=torch.int32, device=p.device)
-    sh = torch.full_like(p, H_SENTINEL, dtype=torch.bfloat16) if shadow else None
-    return p, m, v, t, sh
-
-
-def _step(inp, kind, state, i, ws, groups=None):
-    """One step; with ``groups`` the learning rate and the decay come from their rows (the arguments are unused:
-    0 is passed)."""
-    p, m, v, t, sh = state
-    h = dict(HYPER[kind])
-    lr = h.pop("lr")
-    if groups is not None:
-        lr = 0.0
-        h.pop("weight_decay")
-    out = AllReduceOutput(inp["sums"][i % NGRAD], counts_per_chunk=inp["pc"], geometry=inp["geo"])
-    t.add_(1)
-    out.optim_step_("adamw" if kind == "adamw" else "sgd", p, m, v if kind == "adamw" else None, t, lr, shadow=sh,
-                    max_norm=inp["max_norm"] if ws is not None else None, norm_ws=ws, groups=groups, **h)
 
 
 # 1 -----------------------------------------------------------------------------------------------------------------
@@ -310,82 +246,30 @@ def test_a_schedule_under_replay(src):
 MLP_LRS = (1e-2, 8e-3, 6e-3, 3e-3, 1e-3)
 
 
-def _mlp_run(graphed, wire, bias_decay=0.0, steps=5, load=None, save_at=None):
-    """``steps`` steps of the 64-128-10 MLP at N = 1, a different lr each, the
-    biases in a group of their own.  ``save_at``: also return the state after
-    that many steps; ``load``: such a state, loaded after 2 steps (the run then
-    continues from step ``save_at``)."""
-    from akka_allreduce_amd.models.mlp import MLP, GraphedDPStep, dp_sgd_step, synthetic_batch
-    from akka_allreduce_amd.parallel import FusedAdamW, ThresholdAllreduce
-    from akka_allreduce_amd.parallel.dp import GradientBucket
-
-    dev = _dev()
-    gen = torch.Generator(device=dev).manual_seed(5)
-    batches = [synthetic_batch(32, 64, 10, device=dev, generator=gen) for _ in range(steps)]
-    torch.manual_seed(0)
-    model = MLP(64, 128, 10).to(dev)
-    bucket = GradientBucket(list(model.parameters()), flatten_params=True,
-                            wire_dtype=torch.bfloat16 if wire else None)
-    opt = FusedAdamW(bucket, weight_decay=0.01, max_grad_norm=1.0,
-                     param_groups=[{"params": [model.fc1.bias, model.fc2.bias], "weight_decay": bias_decay}])
-    assert opt.device_lr and len(opt.param_groups) == 2 and len(opt.groups.host_seg_end) == 4
-    ar = ThresholdAllreduce(bucket.numel, max_chunk_size=4096, device=dev,
-                            **({"dtype": torch.bfloat16} if wire else {}))
-    step = None
-    if graphed:
-        step = GraphedDPStep(model, bucket, *batches[0], compute_dtype=torch.bfloat16, optimizer=opt)
-        assert int(opt.t) == 0  # warmup and capture ran forward + backward only
-
-    def one(i):
-        x, y = batches[i]
-        if graphed:
-            return float(step(x, y, MLP_LRS[i], ar))
-        return dp_sgd_step(model, x, y, MLP_LRS[i], ar, bucket, compute_dtype=torch.bfloat16, optimizer=opt)
-
-    losses, order, extra = [], list(range(steps)), {}
-    if load is not None:
-        order = [0, 1] + list(range(load["at"], steps))
-    for n, i in enumerate(order):
-        if load is not None and n == 2:
-            ptrs = step._pointers() if graphed else None
-            with torch.no_grad():
-                bucket.pflat.copy_(load["pflat"])
-            bucket.invalidate_shadow()
-            opt.load_state_dict(load["opt"])
-            if graphed:
-                assert step._pointers() == ptrs
-            assert int(opt.t) == load["at"]
-        losses.append(one(i))
-        if n == 0:
-            extra["after1"] = bucket.pflat.clone()
-        if save_at is not None and n + 1 == save_at:
-            extra["saved"] = {"at": save_at, "pflat": bucket.pflat.clone(), "opt": opt.state_dict()}
-    torch.cuda.synchronize()
-    assert bucket._shadow_on and opt.lr == MLP_LRS[order[-1]]
-    spans = dict(zip(("w1", "b1", "w2", "b2"), bucket.spans()))
-    return dict(losses=losses, pflat=bucket.pflat.clone(), sflat=bucket.sflat.clone(), m=opt.m.clone(),
-                v=opt.v.clone(), t=int(opt.t), spans=spans, **extra)
+def _groups_mlp_run(graphed, wire, bias_decay=0.0, **kw):
+    """A different lr each step, the biases in a group of their own."""
+    return _mlp_run(graphed, wire, lrs=MLP_LRS, bias_decay=bias_decay, **kw)
 
 
 @pytest.mark.parametrize("wire", [False, True])
 def test_graphed_mlp_step_with_param_groups_matches_eager(wire):
-    eager = _mlp_run(False, wire)
-    graphed = _mlp_run(True, wire)
+    eager = _groups_mlp_run(False, wire)
+    graphed = _groups_mlp_run(True, wire)
     assert eager["t"] == 5 and graphed["t"] == 5
     assert eager["losses"] == graphed["losses"], (eager["losses"], graphed["losses"])
     for name in ("pflat", "sflat", "m", "v"):
         assert torch.equal(eager[name], graphed[name]), name
     assert torch.equal(graphed["sflat"], graphed["pflat"].to(torch.bfloat16))
     # the biases are out of the decay: after one step they differ from the run that decays them, the weights do not
-    decayed = _mlp_run(False, wire, bias_decay=0.01, steps=1)
+    decayed = _groups_mlp_run(False, wire, bias_decay=0.01, steps=1)
     for name, (o, n) in eager["spans"].items():
         same = torch.equal(eager["after1"][o:o + n], decayed["after1"][o:o + n])
         assert same == name.startswith("w"), name
 
 
 def test_load_state_dict_into_a_graphed_step_mid_run():
-    eager = _mlp_run(False, False, save_at=3)
-    graphed = _mlp_run(True, False, load=eager["saved"])
+    eager = _groups_mlp_run(False, False, save_at=3)
+    graphed = _groups_mlp_run(True, False, load=eager["saved"])
     assert graphed["t"] == 5
     assert eager["losses"][3:] == graphed["losses"][2:], (eager["losses"], graphed["losses"])
     for name in ("pflat", "sflat", "m", "v"):

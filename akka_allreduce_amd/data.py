@@ -12,6 +12,7 @@ never looks at counts does not pay an extra S-element int32 write per round.
 from __future__ import annotations
 
 import functools
+import math
 from dataclasses import dataclass
 from typing import Any, Optional
 
@@ -87,6 +88,14 @@ def sqnorm_workspace(device) -> torch.Tensor:
 
         n = load().count_sqnorm_partials()
     return torch.zeros(2 + n, dtype=torch.float32, device=device)
+
+
+def guard_state(device) -> torch.Tensor:
+    """The guard record of ``optim_step_(guard=...)`` / ``sqnorm(guard=...)``:
+    int32[4] on ``device``, zeroed once.  ``[0]``: 1 if the last pass was
+    applied, 0 if it was skipped; ``[1]``: steps skipped in total; ``[2]``:
+    steps skipped in a row; ``[3]``: reserved, 0."""
+    return torch.zeros(4, dtype=torch.int32, device=torch.device(device))
 
 
 def _mul32(x: torch.Tensor, c: int) -> torch.Tensor:
@@ -300,7 +309,8 @@ class AllReduceOutput:
                     lr: float, *, weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
                     betas: tuple = (0.9, 0.999), eps: float = 1e-8, shadow: Optional[torch.Tensor] = None,
                     max_norm: Optional[float] = None, norm_ws: Optional[torch.Tensor] = None,
-                    nt: bool = False, groups: Optional[OptimGroups] = None, seed: int = 0) -> torch.Tensor:
+                    nt: bool = False, groups: Optional[OptimGroups] = None, seed: int = 0,
+                    guard: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimizer step of the flat fp32 parameters ``p`` from this
         round, in one fused pass on the GPU: per element ``g = sum / count``,
         then ``kind="sgd"`` (``torch.optim.SGD``: weight decay into ``g``,
@@ -342,7 +352,22 @@ class AllReduceOutput:
         ``seed`` alone (the definition is at the top of the bf16 code in
         ``csrc/kernels/optim.hip``), so ranks that share a seed round alike
         and a replayed capture draws new bits each time.  ``nt`` is not
-        offered with bfloat16 state.  Returns ``p``."""
+        offered with bfloat16 state.
+
+        ``guard`` (``guard_state``) skips a step whose gradient is not finite,
+        on the device.  The norm pass then runs whether or not there is a clip
+        (``norm_ws`` is required) and judges the step by ``sq``, the squared
+        global norm of the round's mean gradient over the elements whose count
+        is > 0: the step is APPLIED iff ``sq`` is a finite fp32 number.  A NaN
+        or an inf in a chunk that has a contributor, or a finite gradient whose
+        squared norm overflows, makes it a SKIPPED step: ``p``, ``m``, ``v``,
+        ``shadow`` and ``t`` keep their bits, and the record counts it
+        (``guard_state``).  With a guard ``t`` is advanced BY THE PASS, and only
+        for an applied step: the caller passes the step before this one and
+        does not advance it, so the bias corrections and the rounding bits of a
+        run with a skipped step are those of a run in which that round never
+        happened.  A non-finite value inside a count-0 chunk is never read and
+        skips nothing.  Returns ``p``."""
         self.wait()
         if kind not in ("sgd", "adamw"):
             raise ValueError(f"optim_step_: kind={kind!r} (sgd or adamw)")
@@ -372,6 +397,9 @@ class AllReduceOutput:
             raise ValueError("optim_step_: t is one int32 on p's device")
         if max_norm is not None and norm_ws is None:
             raise ValueError("optim_step_: max_norm needs a norm workspace (sqnorm_workspace)")
+        if guard is not None and norm_ws is None:
+            raise ValueError("optim_step_: a guard needs a norm workspace (sqnorm_workspace): the norm pass gives "
+                             "the verdict")
         if groups is not None and (groups.numel != d.numel() or groups.rows.device != d.device):
             raise ValueError(f"optim_step_: the groups cover {groups.numel} elements on {groups.rows.device}, the "
                              f"round has {d.numel()} on {d.device}")
@@ -383,7 +411,12 @@ class AllReduceOutput:
                                  "counts (not expanded) and 16-B aligned buffers")
             from ._native_loader import load
 
-            sq = self.sqnorm(norm_ws) if max_norm is not None else None
+            # with a guard the norm pass always runs: it writes the verdict and advances t for an applied step
+            sq = None
+            if guard is not None:
+                sq = self.sqnorm(norm_ws, guard, t)
+            elif max_norm is not None:
+                sq = self.sqnorm(norm_ws)
             pc, table = counts_table(self.counts_per_chunk, self.geometry)
             # the tables stay alive in `groups` until the call returns; nt is not offered with groups
             gr = None if groups is None else (groups.seg_end.data_ptr(), groups.seg_group.data_ptr(),
@@ -394,10 +427,23 @@ class AllReduceOutput:
                                table, t.data_ptr(), sq.data_ptr() if sq is not None else 0,
                                torch.cuda.current_stream(d.device).cuda_stream, bool(nt) and groups is None, lr=lr,
                                weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, beta1=betas[0],
-                               beta2=betas[1], eps=eps, max_norm=max_norm if max_norm is not None else 0.0,
-                               state_dtype=DTYPE_NAME[sdt], seed=seed, groups=gr)
+                               beta2=betas[1], eps=eps,
+                               # a guard without a clip: the pass still takes sq, and an infinite max_norm makes
+                               # its coefficient exactly 1
+                               max_norm=max_norm if max_norm is not None else (math.inf if guard is not None else 0.0),
+                               state_dtype=DTYPE_NAME[sdt], seed=seed, groups=gr,
+                               guard=guard.data_ptr() if guard is not None else 0)
             return p
         # the same formulas as torch operations (count-0 elements keep everything)
+        sq = None
+        if guard is not None:
+            # the verdict first: an applied step advances t before the bias corrections and the rounding bits
+            # read it, a skipped one touches nothing else
+            sq = self.sqnorm(norm_ws, guard, t)
+            if int(guard[0]) == 0:
+                return p
+        elif max_norm is not None:
+            sq = self.sqnorm(norm_ws)
         keep = (self.count <= 0).view_as(p)
         g = self.mean(dtype=torch.float32) if d.dtype != torch.float32 else self.mean()
         g = g.view_as(p)
@@ -406,7 +452,6 @@ class AllReduceOutput:
             m_st, v_st, m, v = m, v, m.float(), v.float() if adam else None
             r_m, r_v = sr_bits(p.numel(), t, seed, p.device)
         if max_norm is not None:
-            sq = self.sqnorm(norm_ws)
             g = g * torch.clamp(max_norm / (sq.sqrt() + 1e-6), max=1.0)
         # the scalars as the kernel receives them, each rounded to fp32 once: a group's rows expanded to
         # per-element vectors, or 0-dim values for the whole buffer
@@ -445,16 +490,31 @@ class AllReduceOutput:
             shadow.copy_(torch.where(keep.view_as(shadow), shadow, p.view_as(shadow).to(shadow.dtype)))
         return p
 
-    def sqnorm(self, ws: torch.Tensor) -> torch.Tensor:
+    def sqnorm(self, ws: torch.Tensor, guard: Optional[torch.Tensor] = None,
+               t: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Squared global norm of this round's mean gradient: the sum over the
         elements whose count is > 0 of ``(sum / count) ** 2``, in fp32, as a
         one-element view of the workspace ``ws`` (``sqnorm_workspace``).  On
         the GPU one pass over the sum (fp32 or bf16), deterministic for a
-        given shape; no host sync."""
+        given shape; no host sync.
+
+        ``guard`` (``guard_state``) and ``t`` (the step, one int32), both or
+        neither: the pass also judges the step.  A finite result: ``guard[0] =
+        1``, ``guard[2] = 0`` and ``t += 1``.  Otherwise ``guard[0] = 0``,
+        ``guard[1] += 1``, ``guard[2] += 1`` and ``t`` stays.  The result has
+        the same bits with and without a guard."""
         self.wait()
         d = self.data
         if ws.dtype != torch.float32 or ws.device != d.device or not ws.is_contiguous():
             raise ValueError("sqnorm: the workspace is float32 on the round's device (sqnorm_workspace)")
+        if (guard is None) != (t is None):
+            raise ValueError("sqnorm: a guard and the step t, both or neither")
+        if guard is not None:
+            if (guard.dtype != torch.int32 or guard.numel() != 4 or guard.device != d.device
+                    or not guard.is_contiguous()):
+                raise ValueError("sqnorm: the guard is int32[4] on the round's device (guard_state)")
+            if t.dtype != torch.int32 or t.numel() != 1 or t.device != d.device:
+                raise ValueError("sqnorm: t is one int32 on the round's device")
         if d.is_cuda:
             from ._native_loader import load
 
@@ -465,10 +525,20 @@ class AllReduceOutput:
             pc, table = counts_table(self.counts_per_chunk, self.geometry)
             # [0]: the result, [1]: the ticket (zero bits), [2:]: one partial per workgroup
             nat.count_sqnorm(ws.data_ptr(), d.data_ptr(), DTYPE_NAME[d.dtype], table, ws.data_ptr() + 8,
-                             ws.data_ptr() + 4, torch.cuda.current_stream(d.device).cuda_stream)
+                             ws.data_ptr() + 4, torch.cuda.current_stream(d.device).cuda_stream,
+                             guard.data_ptr() if guard is not None else 0, t.data_ptr() if t is not None else 0)
             return ws[:1]
         g = self.mean(dtype=torch.float32) if d.dtype != torch.float32 else self.mean()
         ws[0] = (g * g).sum()
+        if guard is not None:
+            if bool(torch.isfinite(ws[0])):
+                guard[0] = 1
+                guard[2] = 0
+                t.add_(1)
+            else:
+                guard[0] = 0
+                guard[1] += 1
+                guard[2] += 1
         return ws[:1]
 
     def mean(self, out: Optional[torch.Tensor] = None, *, dtype: Optional[torch.dtype] = None) -> torch.Tensor:

@@ -215,7 +215,10 @@ class GraphedDPStep:
     the device, so a captured update advances it on every replay; one built with
     ``param_groups`` / ``device_lr`` keeps its learning rate there too, so a
     captured step may be called with another ``lr`` every time (any other rule
-    keeps the one it was captured with, and a different one raises).  The ~30 launches of
+    keeps the one it was captured with, and a different one raises).  An optimizer built with
+    ``skip_nonfinite=True`` drops a replay whose gradient is not finite on the
+    device and counts it (its record is optimizer state: the warm-up puts it
+    back with ``t``).  The ~30 launches of
     the forward/backward cost one replay instead of ~10 µs of host time each
     (the step is otherwise host-bound at this size).
 

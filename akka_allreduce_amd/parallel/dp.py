@@ -219,8 +219,13 @@ class GradientBucket:
         out = self._solo if rule.needs_round else None
         if allreduce is not None:
             out = self._round(allreduce, out_buf)
+        # A rule that may skip the step on the device (skip_nonfinite) then writes no shadow, and the host cannot
+        # know: a shadow that was stale before the pass must not be marked current after it.  Current before, it
+        # is current after either way: a skipped pass leaves the parameters as they were too.
+        stale = getattr(rule, "guard", None) is not None and self._shadow_on \
+            and self._shadow_versions != [p._version for p in self.params]
         rule.apply(self, out, lr, self.sflat if self._shadow_on else None)
-        if out is not None:
+        if out is not None and not stale:
             self.shadow_written()
         return None if allreduce is None else out
 

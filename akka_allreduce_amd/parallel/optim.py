@@ -37,6 +37,18 @@ the shadow from the unrounded moments and rounds only what it stores into
 moving (docs/DESIGN.md).  The rounding bits are a function of the element's
 index, the device step and ``seed``: every rank must use the same seed (the
 default, 0, is), or their parameters drift apart.
+
+``skip_nonfinite=True`` drops a bad step on the device.  The norm pass (which
+then runs with or without a clip) judges the round by the squared global norm
+of its mean gradient: finite, and the step is applied; a NaN, an inf or an
+overflowing norm, and the update pass returns before its first load --
+parameters, moments, shadow and ``t`` keep their bits, and a small device
+record counts the skip (``skipped_steps``, ``skipped_in_a_row``,
+``last_step_applied``).  The norm pass, not ``apply``, then advances ``t``, and
+only for an applied step, so a run with a skipped step continues exactly as a
+run in which that round never happened -- eager and on every replay of a
+captured step.  ``FusedSGD(momentum=0, skip_nonfinite=True)`` is the guarded
+plain SGD (``bucket.sgd`` itself has no norm pass to judge by).
 """
 from __future__ import annotations
 
@@ -44,7 +56,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from ..data import AllReduceOutput, OptimGroups, sqnorm_workspace
+from ..data import AllReduceOutput, OptimGroups, guard_state, sqnorm_workspace
 from .dp import AllreduceFn, GradientBucket
 
 _GROUP_KEYS = ("params", "weight_decay", "lr_scale")
@@ -57,7 +69,7 @@ class _FusedOptimizer:
     needs_round = True  # without an allreduce: the bucket's round of one contributor
 
     def __init__(self, bucket: GradientBucket, max_grad_norm: Optional[float],
-                 state_dtype: torch.dtype = torch.float32, seed: int = 0):
+                 state_dtype: torch.dtype = torch.float32, seed: int = 0, skip_nonfinite: bool = False):
         if bucket.pflat is None or bucket.pflat.dtype != torch.float32 or bucket.flat.dtype != torch.float32:
             raise ValueError(f"{type(self).__name__}: needs GradientBucket(flatten_params=True) with float32 "
                              "parameters")
@@ -67,15 +79,20 @@ class _FusedOptimizer:
             raise ValueError(f"{type(self).__name__}: state_dtype={state_dtype} (torch.float32 or torch.bfloat16)")
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 32:
             raise ValueError(f"{type(self).__name__}: seed={seed!r}, an integer in [0, 2**32)")
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"{type(self).__name__}: skip_nonfinite={skip_nonfinite!r}, True or False")
         self.bucket = bucket
         self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
         self.state_dtype, self.seed = state_dtype, seed
         dev = bucket.pflat.device
         # allocated once: a captured step bakes these pointers in
         self.m = torch.zeros_like(bucket.pflat, dtype=state_dtype)
         self.v: Optional[torch.Tensor] = None
         self.t = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.norm_ws = sqnorm_workspace(dev) if max_grad_norm is not None else None
+        # the norm pass runs for the clip, and for the guard's verdict
+        self.norm_ws = sqnorm_workspace(dev) if (max_grad_norm is not None or skip_nonfinite) else None
+        self.guard = guard_state(dev) if skip_nonfinite else None
         self.device_lr = False
         self.groups: Optional[OptimGroups] = None  # segments and the device rows (device_lr)
         self._group_hyper: List[Dict[str, Any]] = []
@@ -180,13 +197,48 @@ class _FusedOptimizer:
     # ---- state -------------------------------------------------------------------
 
     def state_pointers(self) -> Tuple[int, ...]:
-        """Addresses of everything a captured step reads or writes."""
+        """Addresses of everything a captured step reads or writes.  The guard's record joins them only
+        where the optimizer has one, so without ``skip_nonfinite`` the tuple is what it always was."""
         gr = self.groups
         return tuple(0 if x is None else x.data_ptr() for x in (
-            self.m, self.v, self.t, self.norm_ws, *((gr.rows, gr.seg_end, gr.seg_group) if gr is not None else ())))
+            self.m, self.v, self.t, self.norm_ws,
+            *((self.guard,) if self.guard is not None else ()),
+            *((gr.rows, gr.seg_end, gr.seg_group) if gr is not None else ())))
 
     def state_tensors(self) -> Tuple[torch.Tensor, ...]:
-        return tuple(x for x in (self.m, self.v, self.t) if x is not None)
+        return tuple(x for x in (self.m, self.v, self.t, self.guard) if x is not None)
+
+    # ---- the guard's record ------------------------------------------------------------
+
+    def _need_guard(self, what: str) -> torch.Tensor:
+        if self.guard is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: built without skip_nonfinite")
+        return self.guard
+
+    @property
+    def last_step_applied(self) -> bool:
+        """Was the last step applied (False: skipped, its gradient was not finite)?  A host sync, like
+        ``int(opt.t)``; False before the first step."""
+        return int(self._need_guard("last_step_applied")[0]) == 1
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps skipped in total (a host sync)."""
+        return int(self._need_guard("skipped_steps")[1])
+
+    @property
+    def skipped_in_a_row(self) -> int:
+        """Steps skipped since the last applied one (a host sync)."""
+        return int(self._need_guard("skipped_in_a_row")[2])
+
+    def grad_norm(self) -> torch.Tensor:
+        """The global norm of the last round's mean gradient, as the norm pass left it: a 0-dim device tensor
+        ``sqrt(norm_ws[0])``, no host sync.  Available whenever the optimizer runs a norm pass (a clip or
+        ``skip_nonfinite``); inf or NaN after a skipped step."""
+        if self.norm_ws is None:
+            raise RuntimeError(f"{type(self).__name__}.grad_norm: no norm pass (neither max_grad_norm nor "
+                               "skip_nonfinite)")
+        return self.norm_ws[0].sqrt()
 
     def _hyper_dict(self) -> Dict[str, Any]:
         return {**{k: getattr(self, k) for k in self.hyper}, "max_grad_norm": self.max_grad_norm}
@@ -195,7 +247,9 @@ class _FusedOptimizer:
         """The optimizer's state with cloned tensors (``t`` is read from the device: a host sync)."""
         return {"kind": self.kind, "numel": self.bucket.numel, "t": int(self.t), "m": self.m.clone(),
                 "v": None if self.v is None else self.v.clone(), "hyper": self._hyper_dict(), "lr": self._lr,
-                "param_groups": self.param_groups, "state_dtype": self.state_dtype, "seed": self.seed}
+                "param_groups": self.param_groups, "state_dtype": self.state_dtype, "seed": self.seed,
+                "skip_nonfinite": self.skip_nonfinite,
+                "guard": None if self.guard is None else [int(x) for x in self.guard.tolist()]}
 
     def load_state_dict(self, d: Dict[str, Any]) -> None:
         """Load a ``state_dict`` of an optimizer of the same kind, size and group layout.  Everything is copied
@@ -206,7 +260,11 @@ class _FusedOptimizer:
         ``seed`` is a launch argument too and must match (a dict without one was saved with seed 0).
 
         ``m`` and ``v`` may be float32 or bfloat16 whatever this optimizer's ``state_dtype``: float32 into
-        bfloat16 state rounds to nearest, once; bfloat16 into float32 state is exact.  Any other dtype raises."""
+        bfloat16 state rounds to nearest, once; bfloat16 into float32 state is exact.  Any other dtype raises.
+
+        ``skip_nonfinite`` decides which kernels a capture holds and must match this optimizer's own (a dict
+        saved before the guard existed counts as guard off with zero counters); the guard's record is copied
+        in place."""
         if d.get("kind") != self.kind:
             raise ValueError(f"load_state_dict: kind {d.get('kind')!r}, this optimizer is {self.kind!r}")
         if d.get("numel") != self.bucket.numel:
@@ -233,6 +291,12 @@ class _FusedOptimizer:
         if d.get("seed", 0) != self.seed:
             raise ValueError(f"load_state_dict: seed={d.get('seed', 0)!r}, this optimizer was built with {self.seed!r} "
                              "(a launch argument)")
+        if bool(d.get("skip_nonfinite", False)) != self.skip_nonfinite:
+            raise ValueError(f"load_state_dict: skip_nonfinite={bool(d.get('skip_nonfinite', False))}, this optimizer "
+                             f"was built with {self.skip_nonfinite} (it decides which kernels a capture holds)")
+        record = d.get("guard")
+        if self.guard is not None and record is not None and len(record) != 4:
+            raise ValueError(f"load_state_dict: the guard's record has 4 entries, not {len(record)}")
         if (d.get("v") is None) != (self.v is None):
             raise ValueError("load_state_dict: v does not match the optimizer's kind")
         for name, dst in (("m", self.m), ("v", self.v)):
@@ -242,6 +306,9 @@ class _FusedOptimizer:
         if self.v is not None:
             self.v.copy_(d["v"])
         self.t.fill_(int(d["t"]))
+        if self.guard is not None:
+            self.guard.copy_(torch.tensor([0, 0, 0, 0] if record is None else [int(x) for x in record],
+                                          dtype=torch.int32))
         if self.device_lr:
             for a, b in zip(mine, theirs):
                 a["lr_scale"], a["weight_decay"] = float(b["lr_scale"]), float(b["weight_decay"])
@@ -268,9 +335,10 @@ class _FusedOptimizer:
                 raise RuntimeError(f"{type(self).__name__}: lr={lr} while capturing, the rows hold {self._lr}; call "
                                    "set_lr before the capture")
             self.set_lr(lr)
-        self.t.add_(1)
+        if self.guard is None:
+            self.t.add_(1)  # with a guard the norm pass advances the step, and only for an applied one
         out.optim_step_(self.kind, bucket.pflat, self.m, self.v, self.t, lr, shadow=shadow, max_norm=self.max_grad_norm,
-                        norm_ws=self.norm_ws, groups=self.groups, seed=self.seed,
+                        norm_ws=self.norm_ws, groups=self.groups, seed=self.seed, guard=self.guard,
                         **{k: getattr(self, k) for k in self.hyper})
 
 
@@ -287,18 +355,23 @@ class FusedSGD(_FusedOptimizer):
 
     ``state_dtype=torch.bfloat16`` keeps the momentum in bf16, stored with
     stochastic rounding; ``seed`` keys the rounding bits and must be the same
-    on every rank."""
+    on every rank.
+
+    ``skip_nonfinite=True`` drops a step whose gradient is not finite on the
+    device and counts it (the module's docstring); with ``momentum=0`` this is
+    the guarded plain SGD."""
 
     kind, hyper = "sgd", ("momentum", "nesterov", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, momentum: float = 0.9, nesterov: bool = False,
                  weight_decay: float = 0.0, max_grad_norm: Optional[float] = None, param_groups=None,
-                 device_lr: bool = False, state_dtype: torch.dtype = torch.float32, seed: int = 0):
+                 device_lr: bool = False, state_dtype: torch.dtype = torch.float32, seed: int = 0,
+                 skip_nonfinite: bool = False):
         if momentum < 0 or weight_decay < 0:
             raise ValueError("FusedSGD: momentum and weight_decay are >= 0")
         if nesterov and momentum <= 0:
             raise ValueError("FusedSGD: Nesterov momentum needs momentum > 0")
-        super().__init__(bucket, max_grad_norm, state_dtype, seed)
+        super().__init__(bucket, max_grad_norm, state_dtype, seed, skip_nonfinite)
         self.momentum, self.nesterov, self.weight_decay = float(momentum), bool(nesterov), float(weight_decay)
         self._init_groups(param_groups, device_lr)
 
@@ -306,17 +379,18 @@ class FusedSGD(_FusedOptimizer):
 class FusedAdamW(_FusedOptimizer):
     """``torch.optim.AdamW(betas, eps, weight_decay)`` on a
     ``GradientBucket(flatten_params=True)``, fused into the averaging.
-    ``param_groups`` / ``device_lr`` / ``state_dtype`` / ``seed`` as for
-    ``FusedSGD`` (bf16 state: ``m`` and ``v``)."""
+    ``param_groups`` / ``device_lr`` / ``state_dtype`` / ``seed`` /
+    ``skip_nonfinite`` as for ``FusedSGD`` (bf16 state: ``m`` and ``v``)."""
 
     kind, hyper = "adamw", ("betas", "eps", "weight_decay")
 
     def __init__(self, bucket: GradientBucket, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, max_grad_norm: Optional[float] = None, param_groups=None,
-                 device_lr: bool = False, state_dtype: torch.dtype = torch.float32, seed: int = 0):
+                 device_lr: bool = False, state_dtype: torch.dtype = torch.float32, seed: int = 0,
+                 skip_nonfinite: bool = False):
         if not (0 <= betas[0] < 1 and 0 <= betas[1] < 1) or eps < 0 or weight_decay < 0:
             raise ValueError("FusedAdamW: betas in [0, 1), eps and weight_decay >= 0")
-        super().__init__(bucket, max_grad_norm, state_dtype, seed)
+        super().__init__(bucket, max_grad_norm, state_dtype, seed, skip_nonfinite)
         self.v = torch.zeros_like(self.m)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self._init_groups(param_groups, device_lr)

@@ -1104,14 +1104,16 @@ PYBIND11_MODULE(_native, m) {
                           uintptr_t src, const std::string& src_dtype, const CountsArgs& table, uintptr_t t,
                           uintptr_t sq, uintptr_t stream, bool nt, double lr, double weight_decay, double momentum,
                           bool nesterov, double beta1, double beta2, double eps, double max_norm,
-                          const std::string& state_dtype, uint32_t seed, const std::optional<GroupsArgs>& groups) {
+                          const std::string& state_dtype, uint32_t seed, const std::optional<GroupsArgs>& groups,
+                          uintptr_t guard) {
     AKKA_CHECK(kind == "sgd" || kind == "adamw", "count_optim: kind is 'sgd' or 'adamw'");
     const OptimSpec o{kind == "adamw" ? OptimKind::AdamW : OptimKind::SGD, lr, weight_decay, momentum, nesterov,
                       beta1, beta2, eps, max_norm};
     const OptimBuffers b{reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom), reinterpret_cast<void*>(v),
                          parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
                          reinterpret_cast<const void*>(src), parse_dtype(src_dtype),
-                         reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed};
+                         reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed,
+                         reinterpret_cast<const int32_t*>(guard)};
     OptimGroups g;
     if (groups) g = optim_groups(*groups);
     launch_count_optim(as_stream(stream), b, counts_table(table), o, groups ? &g : nullptr, nt);
@@ -1120,14 +1122,15 @@ PYBIND11_MODULE(_native, m) {
      py::arg("nt") = false, py::kw_only(), py::arg("lr") = 0.0, py::arg("weight_decay") = 0.0,
      py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
      py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("seed") = 0u,
-     py::arg("groups") = py::none());
+     py::arg("groups") = py::none(), py::arg("guard") = 0);
   m.def("count_sqnorm", [](uintptr_t sq, uintptr_t src, const std::string& src_dtype, const CountsArgs& table,
-                           uintptr_t part, uintptr_t ticket, uintptr_t stream) {
+                           uintptr_t part, uintptr_t ticket, uintptr_t stream, uintptr_t guard, uintptr_t t) {
     launch_count_sqnorm(as_stream(stream), reinterpret_cast<float*>(sq), reinterpret_cast<const void*>(src),
                         parse_dtype(src_dtype), counts_table(table), reinterpret_cast<float*>(part),
-                        reinterpret_cast<uint32_t*>(ticket));
+                        reinterpret_cast<uint32_t*>(ticket), reinterpret_cast<int32_t*>(guard),
+                        reinterpret_cast<int32_t*>(t));
   }, py::arg("sq"), py::arg("src"), py::arg("src_dtype"), py::arg("table"), py::arg("part"), py::arg("ticket"),
-     py::arg("stream") = 0);
+     py::arg("stream") = 0, py::arg("guard") = 0, py::arg("t") = 0);
   m.def("count_sqnorm_partials", &count_sqnorm_partials);
   m.def("pack_bf16", [](uintptr_t dst, uintptr_t src, uintptr_t residual, int64_t n, uintptr_t stream) {
     AKKA_CHECK(n >= 0 && (n == 0 || (dst != 0 && src != 0)), "pack_bf16: null buffer");

@@ -83,6 +83,9 @@ struct OptimBuffers {
   const int32_t* t = nullptr;
   const float* sq = nullptr;
   uint32_t seed = 0;
+  // the norm pass's verdict (launch_count_sqnorm with a guard), or null: where guard[0] is 0 the pass returns
+  // before its first load.  Needs sq and t; the norm pass has then advanced t, not the caller.
+  const int32_t* guard = nullptr;
 };
 struct OptimGroups {
   const int64_t* seg_end = nullptr;
@@ -97,8 +100,12 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
 // sq[0] = sum over the elements whose count is > 0 of (src / count)^2.  part:
 // fp32 [count_sqnorm_partials()] workspace; ticket: one uint32 zeroed once
 // (each launch leaves it zero again).  Deterministic for a given shape.
+// guard (int32[4], zeroed once) and t (the step), both or neither: the pass
+// judges the step by sq[0].  Finite: guard[0] = 1, guard[2] = 0, *t += 1.
+// Otherwise: guard[0] = 0, guard[1] and guard[2] += 1, t as it is.  guard[3]
+// is reserved.  sq[0] has the same bits with and without a guard.
 void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const CountsTable& ct, float* part,
-                         uint32_t* ticket);
+                         uint32_t* ticket, int32_t* guard = nullptr, int32_t* t = nullptr);
 int32_t count_sqnorm_partials();
 // q (bf16) = rne(g + r), r = (g + r) - float(q) in place; r may be null (a
 // plain cast).  r becomes 0 where the sum or its rounding is not finite.

@@ -51,6 +51,19 @@
 // partials in index order and re-arms the ticket (the colsum / xent hand-off:
 // no float atomics, no waits).  Same bits for the same shape on every call,
 // and nothing to reset between the replays of a graph.
+//
+// Skipping a non-finite step.  With a guard record (int32[4], zeroed once:
+// {last pass applied, steps skipped in total, skipped in a row, 0}) the norm
+// pass also gives the verdict: the thread that stores sq[0] tests the sum's
+// exponent bits and writes the record with plain stores.  Finite: applied,
+// and it advances the step t -- with a guard the pass owns the step, the caller
+// does not advance it.  Not finite (a NaN or an inf in a chunk with a
+// contributor, or a squared norm that overflows fp32): skipped, counted, t
+// stays.  count_optim with the guard returns before its first load in every
+// workgroup of a skipped step, so p, m, v, the shadow and t keep their bits,
+// and the bias corrections and the rounding key see a run with a skipped step
+// exactly as a run in which that round never happened.  Without a guard both
+// kernels do what they did before it existed.
 #include <hip/hip_runtime.h>
 
 #include "elem.h"
@@ -330,9 +343,13 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
                                                              const int32_t* __restrict__ counts, int64_t S,
                                                              int64_t step, int32_t N, int64_t C, int32_t kmax,
                                                              OptimK k, const int32_t* __restrict__ t,
-                                                             const float* __restrict__ sq, Tail tail) {
+                                                             const float* __restrict__ sq,
+                                                             const int32_t* __restrict__ guard, Tail tail) {
   constexpr bool GROUPS = std::is_same_v<Tail, GroupTail>;
   static_assert(!(GROUPS && NT), "the grouped pass has no nontemporal variant");
+  // a skipped step (the norm pass's verdict, below at count_sqnorm_kernel): wave-uniform, in every workgroup,
+  // before t, sq or anything else is read -- nothing is loaded and nothing is stored
+  if (guard && guard[0] == 0) return;
   const StepCoef sc = step_coefficients<ADAM>(k, t, sq);
   Coef c{};
   if constexpr (!GROUPS) c = lr_coefficients<ADAM>(sc, k.lr, k.eps);
@@ -400,7 +417,8 @@ __global__ __launch_bounds__(kBlock) void count_sqnorm_kernel(float* __restrict_
                                                               const int32_t* __restrict__ counts, int64_t S,
                                                               int64_t step, int32_t N, int64_t C, int32_t kmax,
                                                               float* __restrict__ part,
-                                                              uint32_t* __restrict__ ticket) {
+                                                              uint32_t* __restrict__ ticket,
+                                                              int32_t* __restrict__ guard, int32_t* __restrict__ t) {
   constexpr int E = Elt<TS>::kPerVec;
   __shared__ float red[kBlock / 64 + 1];
   float acc = 0.f;
@@ -471,6 +489,20 @@ __global__ __launch_bounds__(kBlock) void count_sqnorm_kernel(float* __restrict_
   if (threadIdx.x == 0) {
     sq[0] = sum;
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next launch
+    if (guard) {
+      // the verdict: the step is applied iff the sum is a finite fp32 number (its exponent bits are not all
+      // ones).  This thread alone reads and writes the record and the step; the update pass behind this
+      // kernel on the stream sees both across the kernel boundary.
+      if ((__float_as_uint(sum) & 0x7f800000u) != 0x7f800000u) {
+        guard[0] = 1;
+        guard[2] = 0;
+        *t += 1;
+      } else {
+        guard[0] = 0;
+        guard[1] += 1;
+        guard[2] += 1;
+      }
+    }
   }
 }
 
@@ -505,6 +537,7 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
   // bf16 state reads the step for its rounding key, whatever the kind
   AKKA_CHECK(b.p && b.m && b.src && ct.counts && (!adam || (b.v && b.t)) && (!bf_state || b.t),
              "count_optim: null buffer");
+  AKKA_CHECK(!b.guard || (b.sq && b.t), "count_optim: a guard needs the norm pass's sq and the step t");
   AKKA_CHECK(aligned16(b.p) && aligned16(b.m) && aligned16(b.v) && aligned16(b.shadow) && aligned16(b.src),
              "count_optim: buffers must be 16-B aligned");
   ct.check("count_optim");
@@ -550,7 +583,7 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
                                                  decltype(ntv)::value, decltype(tail)>),
                              dim3(rg.grid, rg.split), dim3(kBlock), 0, s, b.p, static_cast<TM*>(b.m),
                              static_cast<TM*>(b.v), static_cast<bf16_t*>(b.shadow), static_cast<const TS*>(b.src),
-                             ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, tail);
+                             ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, b.guard, tail);
         };
         // nontemporal accesses: fp32 state without groups only (checked above)
         if (nt) return launch(Elem<float>{}, std::true_type{}, PlainTail{b.seed});
@@ -570,9 +603,10 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
 int32_t count_sqnorm_partials() { return kMaxGrid; }
 
 void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const CountsTable& ct, float* part,
-                         uint32_t* ticket) {
+                         uint32_t* ticket, int32_t* guard, int32_t* t) {
   if (ct.S <= 0) return;
   AKKA_CHECK(sq && src && ct.counts && part && ticket, "count_sqnorm: null buffer");
+  AKKA_CHECK((guard != nullptr) == (t != nullptr), "count_sqnorm: a guard and a writable step t, both or neither");
   AKKA_CHECK(aligned16(src), "count_sqnorm: the sum must be 16-B aligned");
   ct.check("count_sqnorm");
   // grid * split <= kMaxGrid: one partial each in `part`
@@ -580,7 +614,8 @@ void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt
   // plain loads: the update pass reads the sum next
 #define AKKA_SQ(TS)                                                                                          \
   hipLaunchKernelGGL((count_sqnorm_kernel<TS>), dim3(grid, split), dim3(kBlock), 0, s, sq,                   \
-                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, part, ticket)
+                     static_cast<const TS*>(src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, part, ticket, \
+                     guard, t)
   if (src_dt == DType::BF16) AKKA_SQ(bf16_t);
   else AKKA_SQ(float);
 #undef AKKA_SQ

@@ -90,6 +90,22 @@ def sqnorm_workspace(device) -> torch.Tensor:
     return torch.zeros(2 + n, dtype=torch.float32, device=device)
 
 
+def lamb_workspace(numel: int, layers: int, device) -> torch.Tensor:
+    """Workspace of ``optim_step_(kind="lamb")``: the norm pass's partial sums,
+    one pair of floats (``sum p^2``, ``sum u^2``) per slot and ``tiles + layers``
+    slots, the tile length being the native module's (``lamb_tile``).  Every
+    slot that is read is written by the same step first, so it is allocated
+    once and never reset.  The torch path on the CPU keeps no partials: one
+    pair per layer."""
+    device = torch.device(device)
+    tiles = 0
+    if device.type == "cuda":
+        from ._native_loader import load
+
+        tiles = -(-int(numel) // load().lamb_tile())
+    return torch.zeros(2 * (tiles + int(layers)), dtype=torch.float32, device=device)
+
+
 def guard_state(device) -> torch.Tensor:
     """The guard record of ``optim_step_(guard=...)`` / ``sqnorm(guard=...)``:
     int32[4] on ``device``, zeroed once.  ``[0]``: 1 if the last pass was
@@ -310,7 +326,9 @@ class AllReduceOutput:
                     betas: tuple = (0.9, 0.999), eps: float = 1e-8, shadow: Optional[torch.Tensor] = None,
                     max_norm: Optional[float] = None, norm_ws: Optional[torch.Tensor] = None,
                     nt: bool = False, groups: Optional[OptimGroups] = None, seed: int = 0,
-                    guard: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    guard: Optional[torch.Tensor] = None, lamb_ws: Optional[torch.Tensor] = None,
+                    trust: Optional[torch.Tensor] = None,
+                    layer_adapt: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimizer step of the flat fp32 parameters ``p`` from this
         round, in one fused pass on the GPU: per element ``g = sum / count``,
         then ``kind="sgd"`` (``torch.optim.SGD``: weight decay into ``g``,
@@ -367,11 +385,29 @@ class AllReduceOutput:
         does not advance it, so the bias corrections and the rounding bits of a
         run with a skipped step are those of a run in which that round never
         happened.  A non-finite value inside a count-0 chunk is never read and
-        skips nothing.  Returns ``p``."""
+        skips nothing.
+
+        ``kind="lamb"``: AdamW's ``m`` and ``v`` (the same operations, the
+        same bits), then ``u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p`` and
+        ``p -= lr * r * u`` with one trust ratio ``r`` per LAYER.  It needs
+        ``groups`` with one segment per layer (``lr`` and the decay come from
+        their rows), ``trust`` (float32, one per segment: the pass writes the
+        ratios there and the update reads them), ``layer_adapt`` (int32, one
+        per segment: 0 pins that layer's ``r`` to 1) and ``lamb_ws``
+        (``lamb_workspace``).  ``r = ||p|| / ||u||`` where both norms are
+        positive and finite, else 1; both norms run over the layer's elements
+        whose count is > 0 (``p`` before the step), so a missing chunk enters
+        neither and a layer without a contributor keeps ``r = 1``.  On the GPU
+        three kernels: the norm pass (fixed tiles, one partial pair per tile
+        and layer, no atomics), one workgroup per layer that sums them in a
+        fixed order, and the update -- the same bits for the same inputs on
+        every call, no host sync, nothing to reset.  ``nt`` is refused.
+        Returns ``p``."""
         self.wait()
-        if kind not in ("sgd", "adamw"):
-            raise ValueError(f"optim_step_: kind={kind!r} (sgd or adamw)")
-        adam = kind == "adamw"
+        if kind not in ("sgd", "adamw", "lamb"):
+            raise ValueError(f"optim_step_: kind={kind!r} (sgd, adamw or lamb)")
+        lamb = kind == "lamb"
+        adam = kind == "adamw" or lamb  # a second moment and the bias corrections
         d = self.data
         if d.dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"optim_step_: a float32 or bfloat16 sum, not {d.dtype}")
@@ -403,6 +439,21 @@ class AllReduceOutput:
         if groups is not None and (groups.numel != d.numel() or groups.rows.device != d.device):
             raise ValueError(f"optim_step_: the groups cover {groups.numel} elements on {groups.rows.device}, the "
                              f"round has {d.numel()} on {d.device}")
+        if lamb:
+            if nt:
+                raise ValueError("optim_step_: nt=True is not offered with kind='lamb'")
+            if groups is None:
+                raise ValueError("optim_step_: kind='lamb' needs groups, one segment per layer")
+            nseg = len(groups.host_seg_end)
+            for name, x, dt in (("trust", trust, torch.float32), ("layer_adapt", layer_adapt, torch.int32)):
+                if x is None or x.dtype != dt or x.shape != (nseg,) or x.device != d.device or not x.is_contiguous():
+                    raise ValueError(f"optim_step_: kind='lamb' needs {name}, contiguous {str(dt)[6:]} [{nseg}] "
+                                     "(one per segment) on the round's device")
+            # the size: the launcher checks it against its tiles; the torch path uses none of it
+            if lamb_ws is None or lamb_ws.dtype != torch.float32 or lamb_ws.device != d.device \
+                    or not lamb_ws.is_contiguous():
+                raise ValueError("optim_step_: kind='lamb' needs lamb_ws, a float32 workspace from lamb_workspace "
+                                 "on the round's device")
         if d.is_cuda:
             if not (self._feeds_count_pass() and self._flat_ok(p, torch.float32)
                     and all(self._flat_ok(s, sdt) for _, s in state)
@@ -422,17 +473,30 @@ class AllReduceOutput:
             gr = None if groups is None else (groups.seg_end.data_ptr(), groups.seg_group.data_ptr(),
                                               groups.rows.data_ptr(), groups.host_seg_end, groups.host_seg_group,
                                               groups.ngroups)
+            # a guard without a clip: the pass still takes sq, and an infinite max_norm makes its coefficient
+            # exactly 1
+            mx = max_norm if max_norm is not None else (math.inf if guard is not None else 0.0)
+            stream = torch.cuda.current_stream(d.device).cuda_stream
+            if lamb:
+                # the layers' norms, then their ratios; the launcher checks the workspace's size
+                nat, slots = load(), lamb_ws.numel() // 2
+                if lamb_ws.data_ptr() % 8:
+                    raise ValueError("optim_step_: lamb_ws must be 8-B aligned")
+                nat.lamb_norms(lamb_ws.data_ptr(), slots, p.data_ptr(), m.data_ptr(), v.data_ptr(), d.data_ptr(),
+                               DTYPE_NAME[d.dtype], table, t.data_ptr(), sq.data_ptr() if sq is not None else 0, gr,
+                               stream, beta1=betas[0], beta2=betas[1], eps=eps, max_norm=mx,
+                               state_dtype=DTYPE_NAME[sdt], guard=guard.data_ptr() if guard is not None else 0)
+                nat.lamb_trust(trust.data_ptr(), lamb_ws.data_ptr(), slots, gr, d.numel(), layer_adapt.data_ptr(),
+                               stream, guard.data_ptr() if guard is not None else 0)
             load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
                                shadow.data_ptr() if shadow is not None else 0, d.data_ptr(), DTYPE_NAME[d.dtype],
                                table, t.data_ptr(), sq.data_ptr() if sq is not None else 0,
-                               torch.cuda.current_stream(d.device).cuda_stream, bool(nt) and groups is None, lr=lr,
+                               stream, bool(nt) and groups is None, lr=lr,
                                weight_decay=weight_decay, momentum=momentum, nesterov=nesterov, beta1=betas[0],
-                               beta2=betas[1], eps=eps,
-                               # a guard without a clip: the pass still takes sq, and an infinite max_norm makes
-                               # its coefficient exactly 1
-                               max_norm=max_norm if max_norm is not None else (math.inf if guard is not None else 0.0),
+                               beta2=betas[1], eps=eps, max_norm=mx,
                                state_dtype=DTYPE_NAME[sdt], seed=seed, groups=gr,
-                               guard=guard.data_ptr() if guard is not None else 0)
+                               guard=guard.data_ptr() if guard is not None else 0,
+                               trust=trust.data_ptr() if lamb else 0)
             return p
         # the same formulas as torch operations (count-0 elements keep everything)
         sq = None
@@ -459,7 +523,26 @@ class AllReduceOutput:
             neg_lr, wd, lr_v, decay = (groups.expand(c).view_as(p) for c in range(4))
         else:
             neg_lr, wd, lr_v, decay = OptimGroups.row_values(lr, [(1.0, weight_decay)])[0].to(p.device)
-        if adam:
+        if lamb:
+            b1, b2 = betas
+            tf = t.to(torch.float32)
+            mn = torch.lerp(m, g, 1 - b1)
+            vn = (v * b2).addcmul_(g, g, value=1 - b2)
+            # u as the kernel spells it: (m * (1 / bc1)) / (sqrt(v) / sqrt(bc2) + eps), then wd * p fused in
+            u = torch.addcmul((mn * (1 - b1 ** tf).reciprocal()) / (vn.sqrt() / (1 - b2 ** tf).sqrt()).add_(eps),
+                              p, wd)
+            # the layers' squared norms over the elements that have a contributor
+            ends = torch.tensor(groups.host_seg_end, dtype=torch.int64, device=p.device)
+            lens = torch.diff(ends, prepend=ends.new_zeros(1))
+            layer = torch.repeat_interleave(torch.arange(len(lens), device=p.device), lens)
+            zero = torch.zeros_like(p)
+            pp = torch.zeros(len(lens), device=p.device).index_add_(0, layer, torch.where(keep, zero, p * p))
+            uu = torch.zeros(len(lens), device=p.device).index_add_(0, layer, torch.where(keep, zero, u * u))
+            ok = (pp > 0) & (uu > 0) & torch.isfinite(pp) & torch.isfinite(uu) & (layer_adapt != 0)
+            trust.copy_(torch.where(ok, pp.sqrt() / uu.sqrt(), torch.ones_like(pp)))
+            pn = p
+            step = torch.addcmul(p, u, -(lr_v * trust[layer]))
+        elif adam:
             b1, b2 = betas
             tf = t.to(torch.float32)
             pn = p * decay

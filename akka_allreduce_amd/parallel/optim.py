@@ -49,6 +49,13 @@ only for an applied step, so a run with a skipped step continues exactly as a
 run in which that round never happened -- eager and on every replay of a
 captured step.  ``FusedSGD(momentum=0, skip_nonfinite=True)`` is the guarded
 plain SGD (``bucket.sgd`` itself has no norm pass to judge by).
+
+``FusedLAMB`` adds the layer-wise adaptive rate large global batches want:
+AdamW's moments, and per parameter of the bucket a trust ratio ``||p|| /
+||u||`` computed on the device by a deterministic pass in front of the update
+(its docstring has the rule).  It keeps everything above: the missing-chunk
+semantics (a missing chunk enters no norm), the clip, the guard, bf16 moments,
+the device-resident learning rate, capture.
 """
 from __future__ import annotations
 
@@ -56,7 +63,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from ..data import AllReduceOutput, OptimGroups, guard_state, sqnorm_workspace
+from ..data import AllReduceOutput, OptimGroups, guard_state, lamb_workspace, sqnorm_workspace
 from .dp import AllreduceFn, GradientBucket
 
 _GROUP_KEYS = ("params", "weight_decay", "lr_scale")
@@ -66,6 +73,8 @@ _STATE_DTYPES = (torch.float32, torch.bfloat16)
 class _FusedOptimizer:
     kind = ""
     hyper: Tuple[str, ...] = ()  # the attributes ``optim_step_`` takes as keywords
+    group_keys: Tuple[str, ...] = _GROUP_KEYS  # what a ``param_groups`` entry may hold
+    merge_segments = True  # adjacent parameters of one group are one segment
     needs_round = True  # without an allreduce: the bucket's round of one contributor
 
     def __init__(self, bucket: GradientBucket, max_grad_norm: Optional[float],
@@ -116,9 +125,10 @@ class _FusedOptimizer:
         for gi, g in enumerate(param_groups):
             if not isinstance(g, dict) or "params" not in g:
                 raise ValueError(f"param_groups[{gi}]: a dict with 'params'")
-            unknown = sorted(set(g) - set(_GROUP_KEYS))
+            unknown = sorted(set(g) - set(self.group_keys))
             if unknown:
-                raise ValueError(f"param_groups[{gi}]: unknown key {unknown[0]!r} (known: {', '.join(_GROUP_KEYS)})")
+                raise ValueError(f"param_groups[{gi}]: unknown key {unknown[0]!r} (known: "
+                                 f"{', '.join(self.group_keys)})")
             wd, scale = float(g.get("weight_decay", self.weight_decay)), float(g.get("lr_scale", 1.0))
             if not (wd >= 0 and scale >= 0):
                 raise ValueError(f"param_groups[{gi}]: weight_decay and lr_scale are >= 0")
@@ -134,16 +144,23 @@ class _FusedOptimizer:
                     raise ValueError(f"param_groups[{gi}]: parameter {i} of the bucket is already in group {owner[i]}")
                 owner[i] = gi
             hyper.append({"lr_scale": scale, "weight_decay": wd, "spans": []})
+            if "layer_adaptation" in self.group_keys:
+                adapt = g.get("layer_adaptation", True)
+                if not isinstance(adapt, bool):
+                    raise ValueError(f"param_groups[{gi}]: layer_adaptation={adapt!r}, True or False")
+                hyper[-1]["layer_adaptation"] = adapt
         if any(o is None for o in owner):  # listed nowhere: a last group with the defaults
             hyper.append({"lr_scale": 1.0, "weight_decay": self.weight_decay, "spans": []})
+            if "layer_adaptation" in self.group_keys:
+                hyper[-1]["layer_adaptation"] = True
             owner = [len(hyper) - 1 if o is None else o for o in owner]
-        # adjacent parameters of one group are one segment
+        # adjacent parameters of one group are one segment (not for LAMB: a segment is a layer)
         seg_end: List[int] = []
         seg_group: List[int] = []
         for (off, n), gi in zip(spans, owner):
             if n == 0:
                 continue
-            if seg_group and seg_group[-1] == gi:
+            if self.merge_segments and seg_group and seg_group[-1] == gi:
                 seg_end[-1] = off + n
                 o, k = hyper[gi]["spans"][-1]
                 hyper[gi]["spans"][-1] = (o, k + n)
@@ -159,8 +176,7 @@ class _FusedOptimizer:
     def param_groups(self) -> List[Dict[str, Any]]:
         """Copies of the groups: ``lr_scale``, ``weight_decay`` and the ``spans`` (offset, numel) of the flat
         buffer each one covers.  Change them with ``set_group``."""
-        return [{"lr_scale": g["lr_scale"], "weight_decay": g["weight_decay"], "spans": list(g["spans"])}
-                for g in self._group_hyper]
+        return [{**g, "spans": list(g["spans"])} for g in self._group_hyper]
 
     @property
     def lr(self) -> Optional[float]:
@@ -203,7 +219,12 @@ class _FusedOptimizer:
         return tuple(0 if x is None else x.data_ptr() for x in (
             self.m, self.v, self.t, self.norm_ws,
             *((self.guard,) if self.guard is not None else ()),
-            *((gr.rows, gr.seg_end, gr.seg_group) if gr is not None else ())))
+            *((gr.rows, gr.seg_end, gr.seg_group) if gr is not None else ()),
+            *self._step_buffers().values()))
+
+    def _step_buffers(self) -> Dict[str, torch.Tensor]:
+        """What ``optim_step_`` takes beyond the state, by keyword (LAMB's tables)."""
+        return {}
 
     def state_tensors(self) -> Tuple[torch.Tensor, ...]:
         return tuple(x for x in (self.m, self.v, self.t, self.guard) if x is not None)
@@ -276,6 +297,10 @@ class _FusedOptimizer:
             if [tuple(s) for s in b["spans"]] != [tuple(s) for s in a["spans"]]:
                 raise ValueError(f"load_state_dict: param_groups[{i}] spans {list(b['spans'])}, this optimizer "
                                  f"has {a['spans']}")
+            if "layer_adaptation" in a and bool(b.get("layer_adaptation", True)) != a["layer_adaptation"]:
+                raise ValueError(f"load_state_dict: param_groups[{i}] layer_adaptation="
+                                 f"{bool(b.get('layer_adaptation', True))}, this optimizer was built with "
+                                 f"{a['layer_adaptation']} (a device table of the captured step)")
         hyper = d.get("hyper") or {}
         for k, mine_v in self._hyper_dict().items():
             if k == "weight_decay" and self.device_lr:
@@ -339,7 +364,7 @@ class _FusedOptimizer:
             self.t.add_(1)  # with a guard the norm pass advances the step, and only for an applied one
         out.optim_step_(self.kind, bucket.pflat, self.m, self.v, self.t, lr, shadow=shadow, max_norm=self.max_grad_norm,
                         norm_ws=self.norm_ws, groups=self.groups, seed=self.seed, guard=self.guard,
-                        **{k: getattr(self, k) for k in self.hyper})
+                        **self._step_buffers(), **{k: getattr(self, k) for k in self.hyper})
 
 
 class FusedSGD(_FusedOptimizer):
@@ -394,3 +419,68 @@ class FusedAdamW(_FusedOptimizer):
         self.v = torch.zeros_like(self.m)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self._init_groups(param_groups, device_lr)
+
+
+class FusedLAMB(_FusedOptimizer):
+    """LAMB on a ``GradientBucket(flatten_params=True)``, fused into the
+    averaging: AdamW's moments, then per layer (one parameter of the bucket)
+
+        u = (m / bc1) / (sqrt(v / bc2) + eps) + weight_decay * p
+        r = ||p|| / ||u||  where both are positive and finite, else 1
+        p = p - lr * r * u
+
+    with ``bc_k = 1 - beta_k^t``, ``p`` in ``r`` taken before the step, no clamp
+    on ``r``.  Both norms run over the layer's elements whose chunk had a
+    contributor: a missing chunk (count 0) enters neither norm and keeps ``p``,
+    ``m``, ``v`` and the shadow, and a layer with no contributing element has
+    ``r = 1`` and does not move.  The norms are computed on the device by a
+    pass of their own in front of the update (fixed tiles, partial sums in a
+    fixed order, no atomics): the same inputs give the same bits on every call
+    and every replay of a captured step, with no host sync and nothing to
+    reset.
+
+    The learning rate and the decay always live in the device rows (as with
+    ``device_lr=True``: ``set_lr`` between replays works), and every non-empty
+    parameter is a segment of its own.  ``param_groups`` as for ``FusedSGD``,
+    with one more key: ``layer_adaptation`` (default True); False pins ``r = 1``
+    for that group's layers (biases, norm scales).  ``trust_ratios()`` gives
+    the last step's ratios.  ``state_dtype`` / ``seed`` / ``skip_nonfinite`` /
+    ``max_grad_norm`` as for ``FusedAdamW``; the clip coefficient enters the
+    gradient before the moments."""
+
+    kind, hyper = "lamb", ("betas", "eps", "weight_decay")
+    group_keys = _GROUP_KEYS + ("layer_adaptation",)
+    merge_segments = False
+
+    def __init__(self, bucket: GradientBucket, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.01, max_grad_norm: Optional[float] = None, param_groups=None,
+                 state_dtype: torch.dtype = torch.float32, seed: int = 0, skip_nonfinite: bool = False):
+        if not (0 <= betas[0] < 1 and 0 <= betas[1] < 1) or eps < 0 or weight_decay < 0:
+            raise ValueError("FusedLAMB: betas in [0, 1), eps and weight_decay >= 0")
+        super().__init__(bucket, max_grad_norm, state_dtype, seed, skip_nonfinite)
+        self.v = torch.zeros_like(self.m)
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self._init_groups(param_groups, True)
+        gr, dev = self.groups, bucket.pflat.device
+        nseg = len(gr.host_seg_end)
+        # allocated once, like the state: the per-layer opt-out, the ratios and the norm pass's partials
+        self.layer_adapt = torch.tensor([int(self._group_hyper[g]["layer_adaptation"]) for g in gr.host_seg_group],
+                                        dtype=torch.int32, device=dev)
+        self.trust = torch.ones(nseg, dtype=torch.float32, device=dev)
+        self.lamb_ws = lamb_workspace(bucket.numel, nseg, dev)
+        # each parameter's segment (an empty one has none)
+        self._layer: List[Optional[int]] = []
+        for _, n in bucket.spans():
+            self._layer.append(None if n == 0 else sum(x is not None for x in self._layer))
+
+    def _step_buffers(self) -> Dict[str, torch.Tensor]:
+        return {"lamb_ws": self.lamb_ws, "trust": self.trust, "layer_adapt": self.layer_adapt}
+
+    def state_tensors(self) -> Tuple[torch.Tensor, ...]:
+        """With the trust table: a captured step's warm-up writes it, and it is put back with ``m``, ``v`` and ``t``."""
+        return (*super().state_tensors(), self.trust)
+
+    def trust_ratios(self) -> List[torch.Tensor]:
+        """The trust ratios of the last applied step, one one-element view of the device table per parameter
+        of the bucket (an empty view for an empty parameter), no host sync; 1 before the first step."""
+        return [self.trust[:0] if i is None else self.trust[i:i + 1] for i in self._layer]

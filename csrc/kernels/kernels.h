@@ -54,13 +54,18 @@ void launch_count_mean(hipStream_t s, void* dst, const void* src, const CountsTa
 // from (element index, *t, seed) -- the definition is in optim.hip; p and the
 // shadow come from the unrounded moments.  `t` is then needed for SGD too, and
 // nt is refused.  seed is not used with F32 state.
-enum class OptimKind : int32_t { SGD = 0, AdamW = 1 };
+//
+// LAMB: AdamW's m and v, u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p and
+// p -= lr * r * u with one trust ratio r per layer.  It runs with groups only,
+// one segment per layer, and takes r from groups->trust, which
+// launch_lamb_norms and launch_lamb_trust (below) fill before it.
+enum class OptimKind : int32_t { SGD = 0, AdamW = 1, LAMB = 2 };
 struct OptimSpec {
   OptimKind kind = OptimKind::SGD;
   double lr = 0, weight_decay = 0;
   double momentum = 0;  // SGD
   bool nesterov = false;
-  double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;  // AdamW
+  double beta1 = 0.9, beta2 = 0.999, eps = 1e-8;  // AdamW, LAMB
   double max_norm = 0;                            // used with sq
 };
 // With `groups` the flat buffer is cut into `nseg` segments with one group's
@@ -94,6 +99,7 @@ struct OptimGroups {
   int32_t nseg = 0, ngroups = 0;
   const int64_t* host_seg_end = nullptr;
   const int32_t* host_seg_group = nullptr;
+  const float* trust = nullptr;  // LAMB: device, float[nseg], one trust ratio per segment
 };
 void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
                         const OptimGroups* groups = nullptr, bool nt = false);
@@ -107,6 +113,24 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
 void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt, const CountsTable& ct, float* part,
                          uint32_t* ticket, int32_t* guard = nullptr, int32_t* t = nullptr);
 int32_t count_sqnorm_partials();
+// LAMB's per-layer norms, in two kernels; a layer is a segment of `groups`.
+// launch_lamb_norms reads the sum, the counts, p, m, v, t, sq and the group
+// rows (b, o, ct as for launch_count_optim; it writes none of them) and
+// computes per element the new moments and u exactly as the update pass will.
+// The flat buffer is cut into tiles of lamb_tile() elements; the sums of p^2
+// and of u^2 over a (tile, layer) intersection, count-0 chunks left out, go to
+// part[2 * (tile + layer)] and the float behind it.  part: 8-B aligned, `slots`
+// pairs, at least tiles + layers of them; nothing in it needs a reset, ever.
+// grid: workgroups (0: the launcher's choice); the partials do not depend on it.
+// launch_lamb_trust (one workgroup per layer) sums a layer's partials in slot
+// order and writes trust[layer] = ||p|| / ||u|| where both squared sums are
+// positive and finite, else 1; 1 too where adapt[layer] (device, int32) is 0.
+// With a guard whose verdict is "skipped" both kernels return at once.
+int32_t lamb_tile();
+void launch_lamb_norms(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
+                       const OptimGroups& groups, float* part, int64_t slots, int32_t grid = 0);
+void launch_lamb_trust(hipStream_t s, float* trust, const float* part, int64_t slots, const OptimGroups& groups,
+                       int64_t S, const int32_t* adapt, const int32_t* guard = nullptr);
 // q (bf16) = rne(g + r), r = (g + r) - float(q) in place; r may be null (a
 // plain cast).  r becomes 0 where the sum or its rounding is not finite.
 void launch_pack_bf16(hipStream_t s, void* q, const float* g, float* r, int64_t n);

@@ -1,5 +1,5 @@
 // gfx950 kernels of the fused optimizer step over a round's output: momentum
-// SGD and AdamW straight from the reduced sum and its per-(block, chunk)
+// SGD, AdamW and LAMB straight from the reduced sum and its per-(block, chunk)
 // contributor counts, with an optional global-norm clip.
 //
 // count_optim: one pass.  Per element g = sum / count(chunk), scaled by the
@@ -64,6 +64,34 @@
 // and the bias corrections and the rounding key see a run with a skipped step
 // exactly as a run in which that round never happened.  Without a guard both
 // kernels do what they did before it existed.
+//
+// LAMB.  AdamW's m and v, then per layer L (a segment of the group table, one
+// per parameter)
+//   u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p,   r_L = ||p||_L / ||u||_L,
+//   p = p - lr * r_L * u
+// (the fp32 operation order: at update_one).  r_L is 1 unless both norms are
+// positive and finite, and 1 for a layer that opted out.  Both norms run over
+// the layer's elements whose count is > 0, p before the step: a missing chunk
+// enters neither, and a layer without a contributor keeps r = 1 and does not
+// move.  Three launches: lamb_norms, lamb_trust, count_optim<LAMB>.
+// lamb_norms (at the kernel) recomputes m_new, v_new and u per element in
+// registers with the update's own device function -- the u that is normed and
+// the u that is applied are the same bits, with bf16 moments too -- and leaves
+// one pair of partial sums per (tile, layer) intersection, each in a slot of
+// its own; it writes nothing else.  It reads 16 B per element (fp32 sum and
+// state), the update 30: 46 against AdamW's 30, and the step measured 1.44-1.45x
+// an AdamW step at the config-5 bucket (profiles/r12/fused_lamb/README.md).
+// lamb_trust turns a layer's partials into r_L with one workgroup per layer and
+// a fixed-order sum.  A second kernel and not count_sqnorm's ticket: the kernel
+// boundary is the hand-off, so there is no ticket to re-arm and no
+// written-through partial, and the sum's order is tied to the slots, not to
+// which workgroup arrived last -- the result cannot depend on lamb_norms' grid.
+// The ticket would save one launch of ~10 us in a 400 us step and would need one
+// ticket per layer.  No float atomics, no host sync, nothing to reset between
+// launches or replays; same bits for the same inputs on every call.  With the
+// guard, count_sqnorm runs first and owns t as for the other kinds; after a
+// skipped step lamb_norms and lamb_trust return at once too, so the trust table
+// keeps the last applied step's ratios.
 #include <hip/hip_runtime.h>
 
 #include "elem.h"
@@ -74,6 +102,9 @@
 namespace akka {
 
 namespace {
+
+// The kind of update as a template argument (OptimKind's values).
+enum : int { kSGD = 0, kAdam = 1, kLamb = 2 };
 
 // Host-rounded scalars of one step (each the fp32 torch's kernels receive).
 struct OptimK {
@@ -86,8 +117,9 @@ struct OptimK {
 // Wave-uniform values read from device memory when the kernel runs.
 struct Coef {
   float clip;    // gradient scale
-  float d1, d2;  // AdamW: p += m / (sqrt(v) / d1 + d2)
+  float d1, d2;  // AdamW: p += m / (sqrt(v) / d1 + d2); LAMB: u = (m * d1) / (sqrt(v) / d2 + eps) + wd * p
   bool move;     // with a group table: false for a group whose learning rate is 0
+  float step;    // LAMB: -(lr * r), the layer's trust ratio r folded into the group's learning rate
 };
 
 // The part of them that does not depend on the learning rate: once per kernel.
@@ -96,9 +128,10 @@ struct StepCoef {
   float inv_bc1, sbc2;  // AdamW: 1 / (1 - b1^t), sqrt(1 - b2^t)
 };
 
-template <bool ADAM>
+template <int KIND>
 __device__ __forceinline__ StepCoef step_coefficients(const OptimK& k, const int32_t* t, const float* sq) {
 #pragma clang fp contract(off)
+  constexpr bool ADAM = KIND != kSGD;  // AdamW and LAMB: the moments and their bias corrections
   StepCoef c{1.f, 0.f, 0.f};
   // clip_grad_norm_: min(1, max_norm / (norm + 1e-6)), the quotient as reciprocal * max_norm
   if (sq) c.clip = fminf(1.f, (1.f / (sqrtf(*sq) + 1e-6f)) * k.max_norm);
@@ -112,11 +145,17 @@ __device__ __forceinline__ StepCoef step_coefficients(const OptimK& k, const int
 }
 
 // The part that does: once per kernel, or per group sub-range with a group table.
-template <bool ADAM>
-__device__ __forceinline__ Coef lr_coefficients(const StepCoef& sc, float lr, float eps) {
+// r: the layer's trust ratio (LAMB only).
+template <int KIND>
+__device__ __forceinline__ Coef lr_coefficients(const StepCoef& sc, float lr, float eps, float r = 1.f) {
 #pragma clang fp contract(off)
   Coef c{sc.clip, 0.f, 0.f, lr != 0.f};
-  if constexpr (ADAM) {
+  if constexpr (KIND == kLamb) {
+    c.d1 = sc.inv_bc1;
+    c.d2 = sc.sbc2;
+    c.step = -(lr * r);
+  }
+  if constexpr (KIND == kAdam) {
     // the step size lr / bc1 and sqrt(bc2) folded into the denominator, eps scaled to match:
     // p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
     const float nss = -(sc.inv_bc1 * lr);
@@ -131,15 +170,41 @@ __device__ __forceinline__ Coef lr_coefficients(const StepCoef& sc, float lr, fl
 // group whose learning rate is 0 (a schedule's first step; c.move is false,
 // wave-uniform) advances the state, gives p its decay (a factor of 1) and no
 // step -- the step's formula is 0 / -0 there while v is 0.
-template <bool ADAM, bool GROUPS = false>
-__device__ __forceinline__ void update_one(float g, float& p, float& m, float& v, const OptimK& k, const Coef& c) {
+//
+// LAMB (k.wd: the group's decay; c: lr_coefficients<kLamb>), in this order in fp32:
+//   g  = g * clip
+//   m, v as AdamW's, by the same function (adam_moments)
+//   u  = (m * inv_bc1) / (sqrt(v) / sbc2 + eps)        inv_bc1 = 1 / (1 - b1^t), sbc2 = sqrt(1 - b2^t)
+//   u  = fma(wd, p, u)                                  lamb_u: the norm pass and the update share it
+//   p  = fma(-(lr * r), u, p)                           r: the layer's trust ratio; not where lr == 0
+__device__ __forceinline__ void adam_moments(float g, float& m, float& v, const OptimK& k) {
+#pragma clang fp contract(off)
+  const float d = g - m;  // m = b1 * m + (1 - b1) * g as lerp_ spells it
+  m = k.w1 < 0.5f ? __builtin_fmaf(k.w1, d, m) : __builtin_fmaf(-d, 1.f - k.w1, g);
+  v = __builtin_fmaf(k.w2, g * g, v * k.b2);
+}
+
+// g: the mean gradient before the clip.  m and v become the new moments; returns u.
+__device__ __forceinline__ float lamb_u(float g, float p, float& m, float& v, const OptimK& k, const Coef& c) {
 #pragma clang fp contract(off)
   g = g * c.clip;
-  if constexpr (ADAM) {
+  adam_moments(g, m, v, k);
+  const float u = (m * c.d1) / (sqrtf(v) / c.d2 + k.eps);
+  return __builtin_fmaf(k.wd, p, u);
+}
+
+template <int KIND, bool GROUPS = false>
+__device__ __forceinline__ void update_one(float g, float& p, float& m, float& v, const OptimK& k, const Coef& c) {
+#pragma clang fp contract(off)
+  if constexpr (KIND == kLamb) {
+    const float u = lamb_u(g, p, m, v, k, c);
+    if (c.move) p = __builtin_fmaf(c.step, u, p);
+    return;
+  }
+  g = g * c.clip;
+  if constexpr (KIND == kAdam) {
     p = p * k.decay;
-    const float d = g - m;  // m = b1 * m + (1 - b1) * g as lerp_ spells it
-    m = k.w1 < 0.5f ? __builtin_fmaf(k.w1, d, m) : __builtin_fmaf(-d, 1.f - k.w1, g);
-    v = __builtin_fmaf(k.w2, g * g, v * k.b2);
+    adam_moments(g, m, v, k);
     if (!GROUPS || c.move) p = p + m / (sqrtf(v) / c.d1 + c.d2);
   } else {
     g = __builtin_fmaf(k.wd, p, g);
@@ -192,10 +257,11 @@ __device__ __forceinline__ uint32_t sr_hi(int64_t i, uint32_t key) {
 // scalars: scalar head and tail outside the 8-aligned body, units in between,
 // split over the gridDim.y workgroups that share the region.  TM: the element
 // type of m and v; key: the rounding key (bf16 moments only).
-template <typename TS, typename TM, bool ADAM, bool SHADOW, bool NT, bool GROUPS = false>
+template <typename TS, typename TM, int KIND, bool SHADOW, bool NT, bool GROUPS = false>
 __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restrict__ m, TM* __restrict__ v,
                                              bf16_t* __restrict__ shadow, const TS* __restrict__ src, int64_t s,
                                              int64_t e, float fv, const OptimK& k, const Coef& c, uint32_t key) {
+  constexpr bool ADAM = KIND != kSGD;          // a second moment
   constexpr bool SR = Elt<TM>::kPerVec == 8;  // bf16 moments, stored with stochastic rounding
   static_assert(!(SR && NT), "bf16 moments have no nontemporal variant");
   constexpr int E = 8;                        // elements per unit
@@ -208,7 +274,7 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restri
   const int64_t nv = (e - a) / E;
   auto one = [&](int64_t i) {
     float pi = p[i], mi = Elt<TM>::to_f(m[i]), vi = ADAM ? Elt<TM>::to_f(v[i]) : 0.f;
-    update_one<ADAM, GROUPS>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
+    update_one<KIND, GROUPS>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
     p[i] = pi;
     if constexpr (SR) {
       const uint32_t h = mix32(uint32_t(i) ^ sr_hi(i, key));
@@ -266,7 +332,7 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restri
       for (int q = 0; q < E; ++q) {
         float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = unit_elem<TM>(u.m, q);
         float vi = ADAM ? unit_elem<TM>(u.v, q) : 0.f;
-        update_one<ADAM, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
+        update_one<KIND, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
         pn[q] = pi;
         u.p[q >> 2][q & 3] = __float_as_uint(pi);
         const uint32_t h = mix32((lo | uint32_t(q)) ^ hi);
@@ -283,7 +349,7 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restri
       for (int q = 0; q < E; ++q) {
         float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = __uint_as_float(u.m[q >> 2][q & 3]);
         float vi = ADAM ? __uint_as_float(u.v[q >> 2][q & 3]) : 0.f;
-        update_one<ADAM, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
+        update_one<KIND, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
         pn[q] = pi;
         u.p[q >> 2][q & 3] = __float_as_uint(pi);
         u.m[q >> 2][q & 3] = __float_as_uint(mi);
@@ -329,6 +395,16 @@ struct GroupTail {
   int32_t nseg, G;
   uint32_t seed;
 };
+// LAMB's: the group table with one trust ratio per segment behind it (the ratio
+// kernel's table); a segment is one layer.
+struct LambTail {
+  const int64_t* __restrict__ seg_end;
+  const int32_t* __restrict__ seg_group;
+  const float4* __restrict__ rows;
+  int32_t nseg, G;
+  const float* __restrict__ trust;
+  uint32_t seed;
+};
 
 // Region walk spelled out here as in count_mean, on purpose (the comment at
 // count_mean_kernel, counts.hip).  Tail = PlainTail: one set of scalars for the
@@ -336,7 +412,7 @@ struct GroupTail {
 // intersections with the segments, each processed as the plain pass processes a
 // region, with its group's row.  Everything that picks the segment and the row
 // is wave-uniform (scalar loads, scalar branches).
-template <typename TS, typename TM, bool ADAM, bool SHADOW, bool NT, typename Tail>
+template <typename TS, typename TM, int KIND, bool SHADOW, bool NT, typename Tail>
 __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__ p, TM* __restrict__ m,
                                                              TM* __restrict__ v, bf16_t* __restrict__ shadow,
                                                              const TS* __restrict__ src,
@@ -345,14 +421,15 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
                                                              OptimK k, const int32_t* __restrict__ t,
                                                              const float* __restrict__ sq,
                                                              const int32_t* __restrict__ guard, Tail tail) {
-  constexpr bool GROUPS = std::is_same_v<Tail, GroupTail>;
+  constexpr bool GROUPS = std::is_same_v<Tail, GroupTail> || std::is_same_v<Tail, LambTail>;
+  static_assert((KIND == kLamb) == std::is_same_v<Tail, LambTail>, "LAMB, and LAMB alone, takes the trust table");
   static_assert(!(GROUPS && NT), "the grouped pass has no nontemporal variant");
   // a skipped step (the norm pass's verdict, below at count_sqnorm_kernel): wave-uniform, in every workgroup,
   // before t, sq or anything else is read -- nothing is loaded and nothing is stored
   if (guard && guard[0] == 0) return;
-  const StepCoef sc = step_coefficients<ADAM>(k, t, sq);
+  const StepCoef sc = step_coefficients<KIND>(k, t, sq);
   Coef c{};
-  if constexpr (!GROUPS) c = lr_coefficients<ADAM>(sc, k.lr, k.eps);
+  if constexpr (!GROUPS) c = lr_coefficients<KIND>(sc, k.lr, k.eps);
   uint32_t key = 0;
   if constexpr (Elt<TM>::kPerVec == 8) key = sr_key(tail.seed, t);
   const int64_t nregions = int64_t(N) * kmax;
@@ -388,13 +465,15 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
           kg.wd = r.y;
           kg.lr = r.z;
           kg.decay = r.w;
-          update_range<TS, TM, ADAM, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
-                                                          lr_coefficients<ADAM>(sc, r.z, k.eps), key);
+          float tr = 1.f;
+          if constexpr (KIND == kLamb) tr = tail.trust[si];
+          update_range<TS, TM, KIND, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
+                                                          lr_coefficients<KIND>(sc, r.z, k.eps, tr), key);
         }
         cur = ee;
       }
     } else {
-      update_range<TS, TM, ADAM, SHADOW, NT>(p, m, v, shadow, src, s, e, fv, k, c, key);
+      update_range<TS, TM, KIND, SHADOW, NT>(p, m, v, shadow, src, s, e, fv, k, c, key);
     }
   }
 }
@@ -506,6 +585,181 @@ __global__ __launch_bounds__(kBlock) void count_sqnorm_kernel(float* __restrict_
   }
 }
 
+// LAMB's norm pass (the file header: "LAMB").  The flat buffer is cut into tiles
+// of kLambTile elements (a multiple of the 8-element unit, so a unit never
+// crosses a tile's end); one workgroup takes a tile at a time.  A tile is walked
+// by its intersections with the layers (the segments, found as the grouped pass
+// finds them), a piece by its intersections with the count regions, whose index
+// comes from the geometry arithmetic; a region with count 0 is skipped before
+// any load.  Everything that picks layer, region and count is wave-uniform.
+// Per element m_new, v_new and u come from lamb_u in registers; nothing but the
+// partials is written.  The sums of p^2 and u^2 of a piece go to slot tile +
+// layer: along the pieces either index grows, so no slot is shared, and a
+// layer's pieces are the consecutive slots [first tile + layer, last tile +
+// layer].  Every slot a layer owns is written by every launch (zeros for a piece
+// with no contributor).  A piece's sum depends on the piece alone -- per thread:
+// head, tail, then its units in ascending order; then block_sum -- never on the
+// grid.
+constexpr int kLambTile = 8192;
+static_assert(kLambTile % 8 == 0, "a unit must not cross a tile's end");
+
+template <typename TS, typename TM>
+__device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM* __restrict__ m,
+                                           const TM* __restrict__ v, const TS* __restrict__ src, int64_t s,
+                                           int64_t e, float fv, const OptimK& k, const Coef& c, float& pp, float& uu) {
+#pragma clang fp contract(off)
+  constexpr int E = 8;
+  constexpr int ES = Elt<TS>::kPerVec;
+  constexpr int NS = E / ES;
+  constexpr int NF = E / Elt<float>::kPerVec;
+  constexpr int NM = E / Elt<TM>::kPerVec;
+  int64_t a = (s + E - 1) & ~int64_t(E - 1);
+  if (a > e) a = e;
+  const int64_t nv = (e - a) / E;
+  auto acc = [&](float g, float pi, float mi, float vi) {
+    const float u = lamb_u(g / fv, pi, mi, vi, k, c);
+    pp = pp + pi * pi;
+    uu = uu + u * u;
+  };
+  auto one = [&](int64_t i) { acc(Elt<TS>::to_f(src[i]), p[i], Elt<TM>::to_f(m[i]), Elt<TM>::to_f(v[i])); };
+  for (int64_t i = s + threadIdx.x; i < a; i += kBlock) one(i);
+  for (int64_t i = a + nv * E + threadIdx.x; i < e; i += kBlock) one(i);
+  const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
+  const v4u* p4 = reinterpret_cast<const v4u*>(p + a);
+  const v4u* m4 = reinterpret_cast<const v4u*>(m + a);
+  const v4u* v4 = reinterpret_cast<const v4u*>(v + a);
+  struct Unit {
+    v4u s[NS], p[NF], m[NM], v[NM];
+  };
+  auto load = [&](int64_t at) {
+    Unit u;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) u.s[q] = s4[at * NS + q];
+#pragma unroll
+    for (int q = 0; q < NF; ++q) u.p[q] = p4[at * NF + q];
+#pragma unroll
+    for (int q = 0; q < NM; ++q) u.m[q] = m4[at * NM + q];
+#pragma unroll
+    for (int q = 0; q < NM; ++q) u.v[q] = v4[at * NM + q];
+    return u;
+  };
+  auto sum = [&](const Unit& u) {
+    float g[E];
+#pragma unroll
+    for (int q = 0; q < E; ++q) g[q] = 0.f;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) Elt<TS>::add(reinterpret_cast<float(&)[ES]>(g[q * ES]), u.s[q]);
+#pragma unroll
+    for (int q = 0; q < E; ++q)
+      acc(g[q], __uint_as_float(u.p[q >> 2][q & 3]), unit_elem<TM>(u.m, q), unit_elem<TM>(u.v, q));
+  };
+  int64_t i = threadIdx.x;
+  for (; i + kBlock < nv; i += 2 * kBlock) {
+    const Unit u0 = load(i), u1 = load(i + kBlock);
+    sum(u0);
+    sum(u1);
+  }
+  for (; i < nv; i += kBlock) sum(load(i));
+}
+
+template <typename TS, typename TM>
+__global__ __launch_bounds__(kBlock) void lamb_norms_kernel(float2* __restrict__ part, const float* __restrict__ p,
+                                                            const TM* __restrict__ m, const TM* __restrict__ v,
+                                                            const TS* __restrict__ src,
+                                                            const int32_t* __restrict__ counts, int64_t S,
+                                                            int64_t step, int32_t N, int64_t C, int32_t kmax,
+                                                            OptimK k, const int32_t* __restrict__ t,
+                                                            const float* __restrict__ sq,
+                                                            const int32_t* __restrict__ guard,
+                                                            const int64_t* __restrict__ seg_end,
+                                                            const int32_t* __restrict__ seg_group,
+                                                            const float4* __restrict__ rows, int32_t nseg, int32_t G) {
+  __shared__ float red[kBlock / 64];
+  if (guard && guard[0] == 0) return;  // a skipped step: the partials and the trust table keep what they hold
+  const StepCoef sc = step_coefficients<kLamb>(k, t, sq);
+  const Coef c = lr_coefficients<kLamb>(sc, 0.f, k.eps);  // the step size is the update pass's business
+  const int64_t ntiles = (S + kLambTile - 1) / kLambTile;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t ts = tile * kLambTile;
+    const int64_t te = ts + kLambTile < S ? ts + kLambTile : S;
+    // the first layer whose end is past ts (there is one: the last layer ends at S > ts)
+    int32_t lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+      const int32_t mid = (lo + hi) >> 1;
+      if (seg_end[mid] > ts) hi = mid;
+      else lo = mid + 1;
+    }
+    int64_t cur = ts;
+    for (int32_t li = lo; cur < te && li < nseg; ++li) {
+      const int64_t se = seg_end[li];
+      const int64_t pe = se < te ? se : te;
+      if (pe <= cur) continue;
+      float pp = 0.f, uu = 0.f;
+      const uint32_t g = uint32_t(seg_group[li]);
+      if (g < uint32_t(G)) {  // as in count_optim: a row is never read out of bounds
+        OptimK kg = k;
+        kg.wd = rows[g].y;
+        for (int64_t x = cur; x < pe;) {
+          // the count region of x: block j, chunk kk of it
+          const int64_t jj = step > 0 ? x / step : int64_t(N - 1);
+          const int64_t j = jj < N - 1 ? jj : int64_t(N - 1);
+          const int64_t bs = j * step;
+          const int64_t be = j >= N - 1 ? S : ((j + 1) * step < S ? (j + 1) * step : S);
+          const int64_t kk = (x - bs) / C;
+          int64_t ee = bs + (kk + 1) * C;
+          if (ee > be) ee = be;
+          if (ee > pe) ee = pe;
+          if (ee <= x) ee = pe;  // not with a consistent geometry; the walk must advance
+          // a chunk past kmax has no count: missing, as for the region walks, which never visit it
+          const int32_t cnt = kk < kmax ? counts[j * kmax + kk] : 0;
+          if (cnt > 0) norm_range<TS, TM>(p, m, v, src, x, ee, float(cnt), kg, c, pp, uu);
+          x = ee;
+        }
+      }
+      pp = block_sum(pp, red);
+      uu = block_sum(uu, red);
+      if (threadIdx.x == 0) part[tile + li] = make_float2(pp, uu);
+      cur = pe;
+    }
+  }
+}
+
+// One workgroup per layer: the layer's partials in slot order per thread, then
+// the fixed tree, then r = ||p|| / ||u|| where both squared sums are positive
+// finite numbers, else 1; 1 as well for a layer whose adapt flag is 0.
+__global__ __launch_bounds__(kBlock) void lamb_trust_kernel(float* __restrict__ trust,
+                                                            const float2* __restrict__ part,
+                                                            const int64_t* __restrict__ seg_end,
+                                                            const int32_t* __restrict__ adapt, int32_t nseg,
+                                                            const int32_t* __restrict__ guard) {
+#pragma clang fp contract(off)
+  __shared__ float red[kBlock / 64];
+  if (guard && guard[0] == 0) return;
+  const int32_t li = blockIdx.x;
+  if (li >= nseg) return;
+  if (adapt[li] == 0) {  // wave-uniform: nothing of the partials is read
+    if (threadIdx.x == 0) trust[li] = 1.f;
+    return;
+  }
+  const int64_t ls = li > 0 ? seg_end[li - 1] : 0, le = seg_end[li];
+  float pp = 0.f, uu = 0.f;
+  if (le > ls) {
+    const int64_t first = ls / kLambTile + li, last = (le - 1) / kLambTile + li;
+    for (int64_t i = first + threadIdx.x; i <= last; i += kBlock) {
+      const float2 x = part[i];
+      pp = pp + x.x;
+      uu = uu + x.y;
+    }
+  }
+  pp = block_sum(pp, red);
+  uu = block_sum(uu, red);
+  if (threadIdx.x == 0) {
+    const bool ok = pp > 0.f && uu > 0.f && (__float_as_uint(pp) & 0x7f800000u) != 0x7f800000u &&
+                    (__float_as_uint(uu) & 0x7f800000u) != 0x7f800000u;
+    trust[li] = ok ? sqrtf(pp) / sqrtf(uu) : 1.f;
+  }
+}
+
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // Run-time values as template arguments, in the style of dispatch_int:
@@ -524,41 +778,33 @@ void with_flag(bool b, F&& f) {
   if (b) f(std::true_type{});
   else f(std::false_type{});
 }
+template <typename F>
+void with_kind(OptimKind kind, F&& f) {
+  if (kind == OptimKind::LAMB) f(std::integral_constant<int, kLamb>{});
+  else if (kind == OptimKind::AdamW) f(std::integral_constant<int, kAdam>{});
+  else f(std::integral_constant<int, kSGD>{});
+}
 
-}  // namespace
-
-void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
-                        const OptimGroups* groups, bool nt) {
-  if (ct.S <= 0) return;
-  const bool adam = o.kind == OptimKind::AdamW;
-  const bool bf_state = b.state_dt == DType::BF16;
-  AKKA_CHECK(!(bf_state && nt), "count_optim: no nontemporal variant with bfloat16 state");
-  AKKA_CHECK(!(groups && nt), "count_optim: no nontemporal variant with parameter groups");
-  // bf16 state reads the step for its rounding key, whatever the kind
-  AKKA_CHECK(b.p && b.m && b.src && ct.counts && (!adam || (b.v && b.t)) && (!bf_state || b.t),
-             "count_optim: null buffer");
-  AKKA_CHECK(!b.guard || (b.sq && b.t), "count_optim: a guard needs the norm pass's sq and the step t");
-  AKKA_CHECK(aligned16(b.p) && aligned16(b.m) && aligned16(b.v) && aligned16(b.shadow) && aligned16(b.src),
-             "count_optim: buffers must be 16-B aligned");
-  ct.check("count_optim");
-  if (groups) {
-    const OptimGroups& g = *groups;
-    AKKA_CHECK(g.nseg > 0 && g.ngroups > 0 && g.seg_end && g.seg_group && g.rows && g.host_seg_end &&
-                   g.host_seg_group,
-               "count_optim: no segments, no groups or a null table");
-    AKKA_CHECK(aligned16(g.rows) && (reinterpret_cast<uintptr_t>(g.seg_end) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(g.seg_group) & 3) == 0,
-               "count_optim: the rows must be 16-B aligned, the segment tables naturally");
-    int64_t prev = 0;
-    for (int32_t i = 0; i < g.nseg; ++i) {
-      AKKA_CHECK(g.host_seg_end[i] > prev, "count_optim: segment ends must be positive and ascending");
-      AKKA_CHECK(g.host_seg_group[i] >= 0 && g.host_seg_group[i] < g.ngroups,
-                 "count_optim: a segment's group is outside [0, groups)");
-      prev = g.host_seg_end[i];
-    }
-    AKKA_CHECK(prev == ct.S, "count_optim: the last segment must end at the buffer's size");
+// The host copies of the segment tables against the buffer's size (the kernels trust the device copies).
+void check_groups(const OptimGroups& g, int64_t S, const std::string& who) {
+  AKKA_CHECK(g.nseg > 0 && g.ngroups > 0 && g.seg_end && g.seg_group && g.rows && g.host_seg_end &&
+                 g.host_seg_group,
+             who + ": no segments, no groups or a null table");
+  AKKA_CHECK(aligned16(g.rows) && (reinterpret_cast<uintptr_t>(g.seg_end) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(g.seg_group) & 3) == 0,
+             who + ": the rows must be 16-B aligned, the segment tables naturally");
+  int64_t prev = 0;
+  for (int32_t i = 0; i < g.nseg; ++i) {
+    AKKA_CHECK(g.host_seg_end[i] > prev, who + ": segment ends must be positive and ascending");
+    AKKA_CHECK(g.host_seg_group[i] >= 0 && g.host_seg_group[i] < g.ngroups,
+               who + ": a segment's group is outside [0, groups)");
+    prev = g.host_seg_end[i];
   }
-  // with groups the learning rate and the decay come from the rows (o's are 0 then)
+  AKKA_CHECK(prev == S, who + ": the last segment must end at the buffer's size");
+}
+
+// with groups the learning rate and the decay come from the rows (o's are 0 then)
+OptimK host_scalars(const OptimSpec& o) {
   OptimK k{};
   k.neg_lr = float(-o.lr);
   k.wd = float(o.weight_decay);
@@ -572,23 +818,56 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
   k.w2 = float(1.0 - o.beta2);
   k.eps = float(o.eps);
   k.max_norm = float(o.max_norm);
+  return k;
+}
+
+int64_t lamb_tiles(int64_t S) { return (S + kLambTile - 1) / kLambTile; }
+
+}  // namespace
+
+void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
+                        const OptimGroups* groups, bool nt) {
+  if (ct.S <= 0) return;
+  const bool lamb = o.kind == OptimKind::LAMB;
+  const bool adam = o.kind == OptimKind::AdamW || lamb;  // a second moment and the step
+  const bool bf_state = b.state_dt == DType::BF16;
+  AKKA_CHECK(!(bf_state && nt), "count_optim: no nontemporal variant with bfloat16 state");
+  AKKA_CHECK(!(groups && nt), "count_optim: no nontemporal variant with parameter groups");
+  AKKA_CHECK(!lamb || (groups && groups->trust), "count_optim: LAMB needs groups, one segment per layer, with a "
+                                                 "trust table");
+  // bf16 state reads the step for its rounding key, whatever the kind
+  AKKA_CHECK(b.p && b.m && b.src && ct.counts && (!adam || (b.v && b.t)) && (!bf_state || b.t),
+             "count_optim: null buffer");
+  AKKA_CHECK(!b.guard || (b.sq && b.t), "count_optim: a guard needs the norm pass's sq and the step t");
+  AKKA_CHECK(aligned16(b.p) && aligned16(b.m) && aligned16(b.v) && aligned16(b.shadow) && aligned16(b.src),
+             "count_optim: buffers must be 16-B aligned");
+  ct.check("count_optim");
+  if (groups) check_groups(*groups, ct.S, "count_optim");
+  const OptimK k = host_scalars(o);
   const RegionGrid rg = region_grid(ct.regions(), ct.S, kMaxGrid);
   with_elem(b.src_dt, [&](auto ts) {
-    with_flag(adam, [&](auto ad) {
+    with_kind(o.kind, [&](auto kd) {
       with_flag(b.shadow != nullptr, [&](auto sh) {
         auto launch = [&](auto tm, auto ntv, auto tail) {
           using TS = typename decltype(ts)::type;
           using TM = typename decltype(tm)::type;
-          hipLaunchKernelGGL((count_optim_kernel<TS, TM, decltype(ad)::value, decltype(sh)::value,
-                                                 decltype(ntv)::value, decltype(tail)>),
-                             dim3(rg.grid, rg.split), dim3(kBlock), 0, s, b.p, static_cast<TM*>(b.m),
-                             static_cast<TM*>(b.v), static_cast<bf16_t*>(b.shadow), static_cast<const TS*>(b.src),
-                             ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, b.guard, tail);
+          constexpr int KIND = decltype(kd)::value;
+          // LAMB takes its own tail, the other kinds theirs: the mixed instantiations do not exist
+          if constexpr ((KIND == kLamb) == std::is_same_v<decltype(tail), LambTail>)
+            hipLaunchKernelGGL((count_optim_kernel<TS, TM, KIND, decltype(sh)::value, decltype(ntv)::value,
+                                                   decltype(tail)>),
+                               dim3(rg.grid, rg.split), dim3(kBlock), 0, s, b.p, static_cast<TM*>(b.m),
+                               static_cast<TM*>(b.v), static_cast<bf16_t*>(b.shadow), static_cast<const TS*>(b.src),
+                               ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, b.guard, tail);
         };
         // nontemporal accesses: fp32 state without groups only (checked above)
         if (nt) return launch(Elem<float>{}, std::true_type{}, PlainTail{b.seed});
         with_elem(b.state_dt, [&](auto tm) {
-          if (groups)
+          if (lamb)
+            launch(tm, std::false_type{},
+                   LambTail{groups->seg_end, groups->seg_group, reinterpret_cast<const float4*>(groups->rows),
+                            groups->nseg, groups->ngroups, groups->trust, b.seed});
+          else if (groups)
             launch(tm, std::false_type{},
                    GroupTail{groups->seg_end, groups->seg_group, reinterpret_cast<const float4*>(groups->rows),
                              groups->nseg, groups->ngroups, b.seed});
@@ -620,6 +899,53 @@ void launch_count_sqnorm(hipStream_t s, float* sq, const void* src, DType src_dt
   else AKKA_SQ(float);
 #undef AKKA_SQ
   check_launch("count_sqnorm");
+}
+
+int32_t lamb_tile() { return kLambTile; }
+
+void launch_lamb_norms(hipStream_t s, const OptimBuffers& b, const CountsTable& ct, const OptimSpec& o,
+                       const OptimGroups& groups, float* part, int64_t slots, int32_t grid) {
+  if (ct.S <= 0) return;
+  AKKA_CHECK(b.p && b.m && b.v && b.t && b.src && ct.counts && part, "lamb_norms: null buffer");
+  AKKA_CHECK(!b.guard || b.sq, "lamb_norms: a guard needs the norm pass's sq");
+  AKKA_CHECK(aligned16(b.p) && aligned16(b.m) && aligned16(b.v) && aligned16(b.src) &&
+                 (reinterpret_cast<uintptr_t>(part) & 7) == 0,
+             "lamb_norms: buffers must be 16-B aligned, the partials 8-B");
+  ct.check("lamb_norms");
+  AKKA_CHECK(ct.N > 0 && ct.kmax > 0, "lamb_norms: bad geometry");
+  check_groups(groups, ct.S, "lamb_norms");
+  const int64_t ntiles = lamb_tiles(ct.S);
+  // the last piece writes slot (ntiles - 1) + (nseg - 1)
+  AKKA_CHECK(slots >= ntiles + groups.nseg, "lamb_norms: the workspace needs tiles + layers slots");
+  AKKA_CHECK(grid >= 0, "lamb_norms: grid is >= 0 (0: the launcher's choice)");
+  // any grid gives the same bits: a piece's sum does not depend on which workgroup computed it
+  int64_t g = grid > 0 ? grid : ntiles;
+  if (g > kMaxGrid) g = kMaxGrid;
+  if (g > ntiles) g = ntiles;
+  const OptimK k = host_scalars(o);
+  with_elem(b.src_dt, [&](auto ts) {
+    with_elem(b.state_dt, [&](auto tm) {
+      using TS = typename decltype(ts)::type;
+      using TM = typename decltype(tm)::type;
+      hipLaunchKernelGGL((lamb_norms_kernel<TS, TM>), dim3(int(g)), dim3(kBlock), 0, s,
+                         reinterpret_cast<float2*>(part), b.p, static_cast<const TM*>(b.m),
+                         static_cast<const TM*>(b.v), static_cast<const TS*>(b.src), ct.counts, ct.S, ct.step, ct.N,
+                         ct.C, ct.kmax, k, b.t, b.sq, b.guard, groups.seg_end, groups.seg_group,
+                         reinterpret_cast<const float4*>(groups.rows), groups.nseg, groups.ngroups);
+    });
+  });
+  check_launch("lamb_norms");
+}
+
+void launch_lamb_trust(hipStream_t s, float* trust, const float* part, int64_t slots, const OptimGroups& groups,
+                       int64_t S, const int32_t* adapt, const int32_t* guard) {
+  if (S <= 0) return;
+  AKKA_CHECK(trust && part && adapt && (reinterpret_cast<uintptr_t>(part) & 7) == 0, "lamb_trust: null buffer");
+  check_groups(groups, S, "lamb_trust");
+  AKKA_CHECK(slots >= lamb_tiles(S) + groups.nseg, "lamb_trust: the workspace needs tiles + layers slots");
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3(groups.nseg), dim3(kBlock), 0, s, trust,
+                     reinterpret_cast<const float2*>(part), groups.seg_end, adapt, groups.nseg, guard);
+  check_launch("lamb_trust");
 }
 
 }  // namespace akka

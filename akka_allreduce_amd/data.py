@@ -132,11 +132,23 @@ def sr_bits(n: int, t: torch.Tensor, seed: int, device=None) -> tuple:
     tensors), as the bf16-state pass of ``optim_step_`` draws them: ``key = mix(seed ^ mix(t))``,
     ``h = mix(lo32(i) ^ (hi32(i) * 0x9e3779b9) ^ key)``, ``m`` takes ``h & 0xffff`` and ``v`` ``h >> 16``
     (torch integer ops, int64 masked to 32 bits; the definition is in ``csrc/kernels/optim.hip``)."""
+    h = _sr_hash(n, t, seed, device)
+    return h & 0xFFFF, h >> 16
+
+
+def _sr_hash(n: int, t: torch.Tensor, seed: int, device=None) -> torch.Tensor:
+    """``h(i)`` of ``sr_bits`` for the elements ``0 .. n-1`` (int64 values below 2^32)."""
     device = t.device if device is None else device
     key = _mix32((_mix32(t.reshape(()).to(device=device, dtype=torch.int64) & 0xFFFFFFFF)) ^ int(seed))
     i = torch.arange(n, dtype=torch.int64, device=device)
-    h = _mix32((i & 0xFFFFFFFF) ^ _mul32((i >> 32) & 0xFFFFFFFF, 0x9E3779B9) ^ key)
-    return h & 0xFFFF, h >> 16
+    return _mix32((i & 0xFFFFFFFF) ^ _mul32((i >> 32) & 0xFFFFFFFF, 0x9E3779B9) ^ key)
+
+
+def sr_bits_p(n: int, t: torch.Tensor, seed: int, device=None) -> torch.Tensor:
+    """The 16 rounding bits of a bfloat16 ``p`` for the elements ``0 .. n-1`` at device step ``t`` (an int64
+    tensor): ``h2 & 0xffff`` with ``h2 = mix(h ^ 0x85ebca6b)``, a second hash of the ``h`` of ``sr_bits`` --
+    ``m`` and ``v`` use all 32 bits of ``h`` itself."""
+    return _mix32(_sr_hash(n, t, seed, device) ^ 0x85EBCA6B) & 0xFFFF
 
 
 def sr_bf16(x: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
@@ -372,6 +384,18 @@ class AllReduceOutput:
         and a replayed capture draws new bits each time.  ``nt`` is not
         offered with bfloat16 state.
 
+        ``p`` may be bfloat16 as well (a model trained in pure bf16: ``p`` is
+        the weight the forward reads), with bfloat16 ``m`` / ``v``, no
+        ``shadow`` and no ``nt``; anything else raises.  ``p`` is widened
+        exactly, everything above runs in fp32 on the widened value (LAMB's
+        ``||p||`` included), ``m`` and ``v`` get the bits they would get from
+        an fp32 ``p`` of that value, and only the store of ``p`` is rounded:
+        ``sr_bf16(p_new, r)`` with the 16 bits of ``sr_bits_p``, a second hash
+        of the same (index, ``t``, ``seed``).  Nearest rounding would not do:
+        a step of ``lr * u = 1e-4`` at ``p = 1`` is 1/39 of a bf16 ulp and
+        would never move the parameter.  An element whose fp32 result equals
+        its old value (a zero update, a group at ``lr == 0``) keeps its bits.
+
         ``guard`` (``guard_state``) skips a step whose gradient is not finite,
         on the device.  The norm pass then runs whether or not there is a clip
         (``norm_ws`` is required) and judges the step by ``sq``, the squared
@@ -420,10 +444,20 @@ class AllReduceOutput:
         bf_state = sdt == torch.bfloat16
         if bf_state and nt:
             raise ValueError("optim_step_: nt=True is not offered with bfloat16 state")
+        pdt = p.dtype if p is not None else torch.float32
+        if pdt not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"optim_step_: p is float32 or bfloat16, not {pdt}")
+        bf_param = pdt == torch.bfloat16
+        if bf_param and not bf_state:
+            raise ValueError(f"optim_step_: bfloat16 p needs bfloat16 m and v, not {sdt}")
+        if bf_param and shadow is not None:
+            raise ValueError("optim_step_: no shadow with bfloat16 p (p is the bf16 weight itself)")
+        if bf_param and nt:
+            raise ValueError("optim_step_: nt=True is not offered with bfloat16 p")
         seed = int(seed)
         if not 0 <= seed < 1 << 32:
             raise ValueError(f"optim_step_: seed={seed} is not an unsigned 32-bit value")
-        for name, s, dt in [("p", p, torch.float32)] + [(n, s, sdt) for n, s in state]:
+        for name, s, dt in [("p", p, pdt)] + [(n, s, sdt) for n, s in state]:
             if s is None or not self._flat_ok(s, dt, align=1):
                 raise ValueError(f"optim_step_: {name} must be contiguous {str(dt)[6:]} of the round's size and "
                                  "device")
@@ -455,7 +489,7 @@ class AllReduceOutput:
                 raise ValueError("optim_step_: kind='lamb' needs lamb_ws, a float32 workspace from lamb_workspace "
                                  "on the round's device")
         if d.is_cuda:
-            if not (self._feeds_count_pass() and self._flat_ok(p, torch.float32)
+            if not (self._feeds_count_pass() and self._flat_ok(p, pdt)
                     and all(self._flat_ok(s, sdt) for _, s in state)
                     and (shadow is None or self._flat_ok(shadow, torch.bfloat16))):
                 raise ValueError("optim_step_: the fused pass needs a float32 or bfloat16 sum with its per-chunk "
@@ -477,6 +511,7 @@ class AllReduceOutput:
             # exactly 1
             mx = max_norm if max_norm is not None else (math.inf if guard is not None else 0.0)
             stream = torch.cuda.current_stream(d.device).cuda_stream
+            pk = {"param_dtype": DTYPE_NAME[pdt]} if bf_param else {}  # fp32 p: the calls as they always were
             if lamb:
                 # the layers' norms, then their ratios; the launcher checks the workspace's size
                 nat, slots = load(), lamb_ws.numel() // 2
@@ -485,7 +520,8 @@ class AllReduceOutput:
                 nat.lamb_norms(lamb_ws.data_ptr(), slots, p.data_ptr(), m.data_ptr(), v.data_ptr(), d.data_ptr(),
                                DTYPE_NAME[d.dtype], table, t.data_ptr(), sq.data_ptr() if sq is not None else 0, gr,
                                stream, beta1=betas[0], beta2=betas[1], eps=eps, max_norm=mx,
-                               state_dtype=DTYPE_NAME[sdt], guard=guard.data_ptr() if guard is not None else 0)
+                               state_dtype=DTYPE_NAME[sdt], guard=guard.data_ptr() if guard is not None else 0,
+                               **pk)
                 nat.lamb_trust(trust.data_ptr(), lamb_ws.data_ptr(), slots, gr, d.numel(), layer_adapt.data_ptr(),
                                stream, guard.data_ptr() if guard is not None else 0)
             load().count_optim(kind, p.data_ptr(), m.data_ptr(), v.data_ptr() if adam else 0,
@@ -496,7 +532,7 @@ class AllReduceOutput:
                                beta2=betas[1], eps=eps, max_norm=mx,
                                state_dtype=DTYPE_NAME[sdt], seed=seed, groups=gr,
                                guard=guard.data_ptr() if guard is not None else 0,
-                               trust=trust.data_ptr() if lamb else 0)
+                               trust=trust.data_ptr() if lamb else 0, **pk)
             return p
         # the same formulas as torch operations (count-0 elements keep everything)
         sq = None
@@ -515,6 +551,10 @@ class AllReduceOutput:
             # widened exactly; the formulas run in fp32 and only what is stored into m and v is rounded
             m_st, v_st, m, v = m, v, m.float(), v.float() if adam else None
             r_m, r_v = sr_bits(p.numel(), t, seed, p.device)
+        p_st = p
+        if bf_param:
+            # likewise: the formulas see the widened p, and only what is stored into p is rounded
+            p, r_p = p.float(), sr_bits_p(p.numel(), t, seed, p.device)
         if max_norm is not None:
             g = g * torch.clamp(max_norm / (sq.sqrt() + 1e-6), max=1.0)
         # the scalars as the kernel receives them, each rounded to fp32 once: a group's rows expanded to
@@ -568,6 +608,9 @@ class AllReduceOutput:
             m.copy_(torch.where(keep, m, mn))
             if adam:
                 v.copy_(torch.where(keep, v, vn))
+        if bf_param:
+            p_st.copy_(torch.where(keep, p_st, sr_bf16(pn, r_p.view_as(pn))))
+            return p_st
         p.copy_(torch.where(keep, p, pn))
         if shadow is not None:
             shadow.copy_(torch.where(keep.view_as(shadow), shadow, p.view_as(shadow).to(shadow.dtype)))

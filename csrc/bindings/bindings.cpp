@@ -1110,13 +1110,13 @@ PYBIND11_MODULE(_native, m) {
                           uintptr_t sq, uintptr_t stream, bool nt, double lr, double weight_decay, double momentum,
                           bool nesterov, double beta1, double beta2, double eps, double max_norm,
                           const std::string& state_dtype, uint32_t seed, const std::optional<GroupsArgs>& groups,
-                          uintptr_t guard, uintptr_t trust) {
+                          uintptr_t guard, uintptr_t trust, const std::string& param_dtype) {
     const OptimSpec o{optim_kind(kind), lr, weight_decay, momentum, nesterov, beta1, beta2, eps, max_norm};
-    const OptimBuffers b{reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom), reinterpret_cast<void*>(v),
+    const OptimBuffers b{reinterpret_cast<void*>(p), reinterpret_cast<void*>(mom), reinterpret_cast<void*>(v),
                          parse_dtype(state_dtype), reinterpret_cast<void*>(shadow),
                          reinterpret_cast<const void*>(src), parse_dtype(src_dtype),
                          reinterpret_cast<const int32_t*>(t), reinterpret_cast<const float*>(sq), seed,
-                         reinterpret_cast<const int32_t*>(guard)};
+                         reinterpret_cast<const int32_t*>(guard), parse_dtype(param_dtype)};
     OptimGroups g;
     if (groups) g = optim_groups(*groups);
     g.trust = reinterpret_cast<const float*>(trust);  // LAMB: one ratio per segment
@@ -1126,24 +1126,28 @@ PYBIND11_MODULE(_native, m) {
      py::arg("nt") = false, py::kw_only(), py::arg("lr") = 0.0, py::arg("weight_decay") = 0.0,
      py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("beta1") = 0.9, py::arg("beta2") = 0.999,
      py::arg("eps") = 1e-8, py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("seed") = 0u,
-     py::arg("groups") = py::none(), py::arg("guard") = 0, py::arg("trust") = 0);
+     py::arg("groups") = py::none(), py::arg("guard") = 0, py::arg("trust") = 0,
+     py::arg("param_dtype") = "float32");
   // LAMB's norm pass: the buffers, the table and the hyper-parameters of count_optim(kind="lamb"); part: `slots`
   // pairs of floats; grid 0: the launcher's choice
   m.def("lamb_norms", [](uintptr_t part, int64_t slots, uintptr_t p, uintptr_t mom, uintptr_t v, uintptr_t src,
                          const std::string& src_dtype, const CountsArgs& table, uintptr_t t, uintptr_t sq,
                          const GroupsArgs& groups, uintptr_t stream, double beta1, double beta2, double eps,
-                         double max_norm, const std::string& state_dtype, uintptr_t guard, int32_t grid) {
+                         double max_norm, const std::string& state_dtype, uintptr_t guard, int32_t grid,
+                         const std::string& param_dtype) {
     const OptimSpec o{OptimKind::LAMB, 0.0, 0.0, 0.0, false, beta1, beta2, eps, max_norm};
-    const OptimBuffers b{reinterpret_cast<float*>(p), reinterpret_cast<void*>(mom), reinterpret_cast<void*>(v),
+    const OptimBuffers b{reinterpret_cast<void*>(p), reinterpret_cast<void*>(mom), reinterpret_cast<void*>(v),
                          parse_dtype(state_dtype), nullptr, reinterpret_cast<const void*>(src),
                          parse_dtype(src_dtype), reinterpret_cast<const int32_t*>(t),
-                         reinterpret_cast<const float*>(sq), 0u, reinterpret_cast<const int32_t*>(guard)};
+                         reinterpret_cast<const float*>(sq), 0u, reinterpret_cast<const int32_t*>(guard),
+                         parse_dtype(param_dtype)};
     launch_lamb_norms(as_stream(stream), b, counts_table(table), o, optim_groups(groups),
                       reinterpret_cast<float*>(part), slots, grid);
   }, py::arg("part"), py::arg("slots"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("src"),
      py::arg("src_dtype"), py::arg("table"), py::arg("t"), py::arg("sq"), py::arg("groups"), py::arg("stream") = 0,
      py::kw_only(), py::arg("beta1") = 0.9, py::arg("beta2") = 0.999, py::arg("eps") = 1e-8,
-     py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("guard") = 0, py::arg("grid") = 0);
+     py::arg("max_norm") = 0.0, py::arg("state_dtype") = "float32", py::arg("guard") = 0, py::arg("grid") = 0,
+     py::arg("param_dtype") = "float32");
   m.def("lamb_trust", [](uintptr_t trust, uintptr_t part, int64_t slots, const GroupsArgs& groups, int64_t S,
                          uintptr_t adapt, uintptr_t stream, uintptr_t guard) {
     launch_lamb_trust(as_stream(stream), reinterpret_cast<float*>(trust), reinterpret_cast<const float*>(part),

@@ -3,7 +3,7 @@
 // and the scalar conversions.  Sums accumulate in fp32; bf16 is rounded in one
 // place (Elt<bf16_t>::from_f), so a sum is the same bits whichever kernel made
 // it; the one other rounding is sr_bf16 below, the stochastic one of the
-// optimizer's bf16 moments.  Only to be included by .hip translation units.
+// optimizer's bf16 moments and bf16 parameters.  Only to be included by .hip translation units.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -54,6 +54,10 @@ void launch_count_mean(hipStream_t s, void* dst, const void* src, const CountsTa
 // from (element index, *t, seed) -- the definition is in optim.hip; p and the
 // shadow come from the unrounded moments.  `t` is then needed for SGD too, and
 // nt is refused.  seed is not used with F32 state.
+// param_dt: the element type of p, F32 or BF16.  BF16 parameters need BF16
+// state and take neither a shadow nor nt (refused).  They are widened on load,
+// everything is computed as for an fp32 p of that value, and the store of p is
+// rounded stochastically with a second hash of (element index, *t, seed).
 //
 // LAMB: AdamW's m and v, u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p and
 // p -= lr * r * u with one trust ratio r per layer.  It runs with groups only,
@@ -79,7 +83,7 @@ struct OptimSpec {
 // is refused.  A group whose lr is 0 advances m and v and leaves p (times its
 // decay of 1) in place.
 struct OptimBuffers {
-  float* p = nullptr;
+  void* p = nullptr;
   void *m = nullptr, *v = nullptr;
   DType state_dt = DType::F32;
   void* shadow = nullptr;
@@ -91,6 +95,9 @@ struct OptimBuffers {
   // the norm pass's verdict (launch_count_sqnorm with a guard), or null: where guard[0] is 0 the pass returns
   // before its first load.  Needs sq and t; the norm pass has then advanced t, not the caller.
   const int32_t* guard = nullptr;
+  // the element type of p, F32 or BF16.  BF16 parameters (with BF16 state only, no shadow, no nt) are widened on
+  // load, updated in fp32 and stored with stochastic rounding from a second hash of (index, *t, seed): optim.hip
+  DType param_dt = DType::F32;
 };
 struct OptimGroups {
   const int64_t* seg_end = nullptr;

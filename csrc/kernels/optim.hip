@@ -10,6 +10,9 @@
 // and v are fp32, or bf16 stored with stochastic rounding (below, in front of
 // update_range); the sum is fp32 or bf16 (a compressed wire's sum, read wide
 // into fp32); an optional bf16 shadow receives bf16(p_new) from the same pass.
+// p may be bf16 too (a model trained in pure bf16; with bf16 moments only, no
+// shadow: p is the weight the forward reads): widened on load, the same fp32
+// arithmetic, the store rounded stochastically ("bf16 parameters" below).
 //
 // Count 0 means MISSING, not zero: a chunk no contributor reached leaves p, m,
 // v and the shadow untouched -- the region is skipped before any load.  With
@@ -24,8 +27,8 @@
 // Region walk as count_mean (counts.hip): one workgroup per (block, chunk)
 // region at a time, the count a wave-uniform scalar, gridDim.y workgroups
 // sharing a region while there are few.  A unit is 8 elements: one 16-B
-// vector of a bf16 sum or two of an fp32 one, two each of p, m and v, one of
-// the shadow -- every stream moves 16 B per access.  Elements of a region
+// vector of a bf16 sum or two of an fp32 one, two each of fp32 p, m and v, one
+// each of bf16 ones, one of the shadow -- every stream moves 16 B per access.  Elements of a region
 // outside its 8-aligned body go through the scalar path.  Two units per
 // thread, every load of both in flight before the first store.
 //
@@ -38,7 +41,15 @@
 // size; `nt` is kept so that bench/fused_opt.py can repeat the comparison
 // (table in profiles/r08/fused_opt/README.md).  bf16 moments take 4 B per
 // element off SGD and 8 B off AdamW, and the time follows the bytes
-// (profiles/r10/bf16_state/README.md).
+// (profiles/r10/bf16_state/README.md).  bf16 parameters take 4 B more off
+// either and the shadow's 2 B with them; from a bf16 sum, per element:
+//                                      sum  p  m  v  shadow  total
+//   AdamW, bf16 moments, fp32 p         2   8  4  4    2      20
+//   AdamW, bf16 moments, bf16 p         2   4  4  4    -      14
+//   SGD,   bf16 moments, fp32 p         2   8  4  -    2      16
+//   SGD,   bf16 moments, bf16 p         2   4  4  -    -      10
+// Plain accesses only, as for bf16 moments: there is no nontemporal variant
+// (profiles/r13/bf16_params/README.md has the times).
 //
 // With a group table the same kernel takes each group's weight decay and
 // learning rate from a small device table when it runs (below, at the kernel);
@@ -244,6 +255,25 @@ __device__ __forceinline__ void update_one(float g, float& p, float& m, float& v
 // of m and v go through sr, so p is bitwise what the fp32-state pass gives from
 // the widened state.  A unit is still 8 elements, m and v one 16-B vector each.
 // Nontemporal accesses are not offered with bf16 moments (the launcher refuses).
+//
+// bf16 parameters (TP = bf16_t; with bf16 moments only, no shadow, no
+// nontemporal variant -- the launcher refuses the rest and no other
+// instantiation exists).  p is one 16-B vector per unit, loaded with the other
+// streams, widened exactly (unit_elem), and update_one, lamb_u and the
+// coefficients run on the widened value as they are: m and v get the bits the
+// fp32-p pass gives from that value.  Only the store of p is rounded, and
+// stochastically for the reason given for v: lr * u = 1e-4 at p = 1 is 1/39 of
+// a bf16 ulp, and a nearest-rounded parameter never moves.  Definition, with
+// h(i), mix and sr from above:
+//   h2(i) = mix(h(i) ^ 0x85ebca6b)
+//   p takes r = h2(i) & 0xffff;   stored p = sr(p_new, r)
+// A second hash and not a third slice of h: h has 32 bits and m and v use them
+// all.  h2 depends on (index, device step, seed) alone, like h.  An element
+// whose fp32 p_new equals its widened old p (a zero update; a group at lr == 0,
+// where AdamW's decay factor is exactly 1) keeps its bits: the low 16 bits of
+// p_new are zero and r < 2^16 carries nothing.  Count-0 regions and a skipped
+// step return before any load, as ever.  LAMB's norm pass reads the same
+// widened p, before the step.
 __device__ __forceinline__ uint32_t sr_key(uint32_t seed, const int32_t* t) {
   return mix32(seed ^ mix32(uint32_t(*t)));
 }
@@ -253,34 +283,42 @@ __device__ __forceinline__ uint32_t sr_hi(int64_t i, uint32_t key) {
   return (uint32_t(uint64_t(i) >> 32) * 0x9e3779b9u) ^ key;
 }
 
+// h2 from the element's h: the bits of a bf16 parameter's store.
+__device__ __forceinline__ uint32_t sr_h2(uint32_t h) { return mix32(h ^ 0x85ebca6bu); }
+
 // The elements [s, e) of one count region (fv: its count) with one set of
 // scalars: scalar head and tail outside the 8-aligned body, units in between,
 // split over the gridDim.y workgroups that share the region.  TM: the element
-// type of m and v; key: the rounding key (bf16 moments only).
-template <typename TS, typename TM, int KIND, bool SHADOW, bool NT, bool GROUPS = false>
-__device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restrict__ m, TM* __restrict__ v,
+// type of m and v; TP: that of p; key: the rounding key (bf16 moments only).
+template <typename TS, typename TM, typename TP, int KIND, bool SHADOW, bool NT, bool GROUPS = false>
+__device__ __forceinline__ void update_range(TP* __restrict__ p, TM* __restrict__ m, TM* __restrict__ v,
                                              bf16_t* __restrict__ shadow, const TS* __restrict__ src, int64_t s,
                                              int64_t e, float fv, const OptimK& k, const Coef& c, uint32_t key) {
   constexpr bool ADAM = KIND != kSGD;          // a second moment
   constexpr bool SR = Elt<TM>::kPerVec == 8;  // bf16 moments, stored with stochastic rounding
+  constexpr bool PB = Elt<TP>::kPerVec == 8;  // bf16 parameters: widened on load, the store rounded with h2
   static_assert(!(SR && NT), "bf16 moments have no nontemporal variant");
+  static_assert(!PB || (SR && !SHADOW), "bf16 parameters: bf16 moments, no shadow");
   constexpr int E = 8;                        // elements per unit
   constexpr int ES = Elt<TS>::kPerVec;        // elements per source vector
   constexpr int NS = E / ES;                  // source vectors per unit
   constexpr int NF = E / Elt<float>::kPerVec; // fp32 vectors per unit and stream
   constexpr int NM = E / Elt<TM>::kPerVec;    // vectors of m (and of v) per unit
+  constexpr int NP = E / Elt<TP>::kPerVec;    // vectors of p per unit
   int64_t a = (s + E - 1) & ~int64_t(E - 1);  // first element 16-B aligned in every stream
   if (a > e) a = e;
   const int64_t nv = (e - a) / E;
   auto one = [&](int64_t i) {
-    float pi = p[i], mi = Elt<TM>::to_f(m[i]), vi = ADAM ? Elt<TM>::to_f(v[i]) : 0.f;
+    float pi = Elt<TP>::to_f(p[i]), mi = Elt<TM>::to_f(m[i]), vi = ADAM ? Elt<TM>::to_f(v[i]) : 0.f;
     update_one<KIND, GROUPS>(Elt<TS>::to_f(src[i]) / fv, pi, mi, vi, k, c);
-    p[i] = pi;
     if constexpr (SR) {
       const uint32_t h = mix32(uint32_t(i) ^ sr_hi(i, key));
+      if constexpr (PB) p[i] = sr_bf16(pi, sr_h2(h) & 0xffffu);
+      else p[i] = pi;
       m[i] = sr_bf16(mi, h & 0xffffu);
       if constexpr (ADAM) v[i] = sr_bf16(vi, h >> 16);
     } else {
+      p[i] = pi;
       m[i] = mi;
       if constexpr (ADAM) v[i] = vi;
     }
@@ -301,14 +339,14 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restri
     else *q = x;
   };
   struct Unit {
-    v4u s[NS], p[NF], m[NM], v[NM];
+    v4u s[NS], p[NP], m[NM], v[NM];
   };
   auto load = [&](int64_t at) {
     Unit u;
 #pragma unroll
     for (int q = 0; q < NS; ++q) u.s[q] = ld(s4 + at * NS + q);
 #pragma unroll
-    for (int q = 0; q < NF; ++q) u.p[q] = ld(p4 + at * NF + q);
+    for (int q = 0; q < NP; ++q) u.p[q] = ld(p4 + at * NP + q);
 #pragma unroll
     for (int q = 0; q < NM; ++q) u.m[q] = ld(m4 + at * NM + q);
     if constexpr (ADAM) {
@@ -328,19 +366,27 @@ __device__ __forceinline__ void update_range(float* __restrict__ p, TM* __restri
       const int64_t i0 = a + at * E;
       const uint32_t lo = uint32_t(i0), hi = sr_hi(i0, key);
       uint32_t mo[E], vo[E];
+      [[maybe_unused]] uint32_t po[PB ? E : 1];  // bf16 p: the rounded halves
 #pragma unroll
       for (int q = 0; q < E; ++q) {
-        float pi = __uint_as_float(u.p[q >> 2][q & 3]), mi = unit_elem<TM>(u.m, q);
+        float pi, mi = unit_elem<TM>(u.m, q);
+        if constexpr (PB) pi = unit_elem<TP>(u.p, q);
+        else pi = __uint_as_float(u.p[q >> 2][q & 3]);
         float vi = ADAM ? unit_elem<TM>(u.v, q) : 0.f;
         update_one<KIND, GROUPS>(g[q] / fv, pi, mi, vi, k, c);
         pn[q] = pi;
-        u.p[q >> 2][q & 3] = __float_as_uint(pi);
+        if constexpr (!PB) u.p[q >> 2][q & 3] = __float_as_uint(pi);
         const uint32_t h = mix32((lo | uint32_t(q)) ^ hi);
+        if constexpr (PB) po[q] = sr_bf16(pi, sr_h2(h) & 0xffffu);
         mo[q] = sr_bf16(mi, h & 0xffffu);
         if constexpr (ADAM) vo[q] = sr_bf16(vi, h >> 16);
       }
+      if constexpr (PB) {
+        st(v4u{po[0] | (po[1] << 16), po[2] | (po[3] << 16), po[4] | (po[5] << 16), po[6] | (po[7] << 16)}, p4 + at);
+      } else {
 #pragma unroll
-      for (int q = 0; q < NF; ++q) st(u.p[q], p4 + at * NF + q);
+        for (int q = 0; q < NF; ++q) st(u.p[q], p4 + at * NF + q);
+      }
       st(v4u{mo[0] | (mo[1] << 16), mo[2] | (mo[3] << 16), mo[4] | (mo[5] << 16), mo[6] | (mo[7] << 16)}, m4 + at);
       if constexpr (ADAM)
         st(v4u{vo[0] | (vo[1] << 16), vo[2] | (vo[3] << 16), vo[4] | (vo[5] << 16), vo[6] | (vo[7] << 16)}, v4 + at);
@@ -412,8 +458,8 @@ struct LambTail {
 // intersections with the segments, each processed as the plain pass processes a
 // region, with its group's row.  Everything that picks the segment and the row
 // is wave-uniform (scalar loads, scalar branches).
-template <typename TS, typename TM, int KIND, bool SHADOW, bool NT, typename Tail>
-__global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__ p, TM* __restrict__ m,
+template <typename TS, typename TM, typename TP, int KIND, bool SHADOW, bool NT, typename Tail>
+__global__ __launch_bounds__(kBlock) void count_optim_kernel(TP* __restrict__ p, TM* __restrict__ m,
                                                              TM* __restrict__ v, bf16_t* __restrict__ shadow,
                                                              const TS* __restrict__ src,
                                                              const int32_t* __restrict__ counts, int64_t S,
@@ -467,13 +513,13 @@ __global__ __launch_bounds__(kBlock) void count_optim_kernel(float* __restrict__
           kg.decay = r.w;
           float tr = 1.f;
           if constexpr (KIND == kLamb) tr = tail.trust[si];
-          update_range<TS, TM, KIND, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
-                                                          lr_coefficients<KIND>(sc, r.z, k.eps, tr), key);
+          update_range<TS, TM, TP, KIND, SHADOW, false, true>(p, m, v, shadow, src, cur, ee, fv, kg,
+                                                              lr_coefficients<KIND>(sc, r.z, k.eps, tr), key);
         }
         cur = ee;
       }
     } else {
-      update_range<TS, TM, KIND, SHADOW, NT>(p, m, v, shadow, src, s, e, fv, k, c, key);
+      update_range<TS, TM, TP, KIND, SHADOW, NT>(p, m, v, shadow, src, s, e, fv, k, c, key);
     }
   }
 }
@@ -603,8 +649,8 @@ __global__ __launch_bounds__(kBlock) void count_sqnorm_kernel(float* __restrict_
 constexpr int kLambTile = 8192;
 static_assert(kLambTile % 8 == 0, "a unit must not cross a tile's end");
 
-template <typename TS, typename TM>
-__device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM* __restrict__ m,
+template <typename TS, typename TM, typename TP>
+__device__ __forceinline__ void norm_range(const TP* __restrict__ p, const TM* __restrict__ m,
                                            const TM* __restrict__ v, const TS* __restrict__ src, int64_t s,
                                            int64_t e, float fv, const OptimK& k, const Coef& c, float& pp, float& uu) {
 #pragma clang fp contract(off)
@@ -613,6 +659,8 @@ __device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM
   constexpr int NS = E / ES;
   constexpr int NF = E / Elt<float>::kPerVec;
   constexpr int NM = E / Elt<TM>::kPerVec;
+  constexpr int NP = E / Elt<TP>::kPerVec;  // bf16 parameters are read widened, as the update reads them
+  static_assert(NP == NF || NM == 1, "bf16 parameters: bf16 moments");
   int64_t a = (s + E - 1) & ~int64_t(E - 1);
   if (a > e) a = e;
   const int64_t nv = (e - a) / E;
@@ -621,7 +669,9 @@ __device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM
     pp = pp + pi * pi;
     uu = uu + u * u;
   };
-  auto one = [&](int64_t i) { acc(Elt<TS>::to_f(src[i]), p[i], Elt<TM>::to_f(m[i]), Elt<TM>::to_f(v[i])); };
+  auto one = [&](int64_t i) {
+    acc(Elt<TS>::to_f(src[i]), Elt<TP>::to_f(p[i]), Elt<TM>::to_f(m[i]), Elt<TM>::to_f(v[i]));
+  };
   for (int64_t i = s + threadIdx.x; i < a; i += kBlock) one(i);
   for (int64_t i = a + nv * E + threadIdx.x; i < e; i += kBlock) one(i);
   const v4u* s4 = reinterpret_cast<const v4u*>(src + a);
@@ -629,14 +679,14 @@ __device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM
   const v4u* m4 = reinterpret_cast<const v4u*>(m + a);
   const v4u* v4 = reinterpret_cast<const v4u*>(v + a);
   struct Unit {
-    v4u s[NS], p[NF], m[NM], v[NM];
+    v4u s[NS], p[NP], m[NM], v[NM];
   };
   auto load = [&](int64_t at) {
     Unit u;
 #pragma unroll
     for (int q = 0; q < NS; ++q) u.s[q] = s4[at * NS + q];
 #pragma unroll
-    for (int q = 0; q < NF; ++q) u.p[q] = p4[at * NF + q];
+    for (int q = 0; q < NP; ++q) u.p[q] = p4[at * NP + q];
 #pragma unroll
     for (int q = 0; q < NM; ++q) u.m[q] = m4[at * NM + q];
 #pragma unroll
@@ -651,7 +701,7 @@ __device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM
     for (int q = 0; q < NS; ++q) Elt<TS>::add(reinterpret_cast<float(&)[ES]>(g[q * ES]), u.s[q]);
 #pragma unroll
     for (int q = 0; q < E; ++q)
-      acc(g[q], __uint_as_float(u.p[q >> 2][q & 3]), unit_elem<TM>(u.m, q), unit_elem<TM>(u.v, q));
+      acc(g[q], unit_elem<TP>(u.p, q), unit_elem<TM>(u.m, q), unit_elem<TM>(u.v, q));
   };
   int64_t i = threadIdx.x;
   for (; i + kBlock < nv; i += 2 * kBlock) {
@@ -662,8 +712,8 @@ __device__ __forceinline__ void norm_range(const float* __restrict__ p, const TM
   for (; i < nv; i += kBlock) sum(load(i));
 }
 
-template <typename TS, typename TM>
-__global__ __launch_bounds__(kBlock) void lamb_norms_kernel(float2* __restrict__ part, const float* __restrict__ p,
+template <typename TS, typename TM, typename TP>
+__global__ __launch_bounds__(kBlock) void lamb_norms_kernel(float2* __restrict__ part, const TP* __restrict__ p,
                                                             const TM* __restrict__ m, const TM* __restrict__ v,
                                                             const TS* __restrict__ src,
                                                             const int32_t* __restrict__ counts, int64_t S,
@@ -712,7 +762,7 @@ __global__ __launch_bounds__(kBlock) void lamb_norms_kernel(float2* __restrict__
           if (ee <= x) ee = pe;  // not with a consistent geometry; the walk must advance
           // a chunk past kmax has no count: missing, as for the region walks, which never visit it
           const int32_t cnt = kk < kmax ? counts[j * kmax + kk] : 0;
-          if (cnt > 0) norm_range<TS, TM>(p, m, v, src, x, ee, float(cnt), kg, c, pp, uu);
+          if (cnt > 0) norm_range<TS, TM, TP>(p, m, v, src, x, ee, float(cnt), kg, c, pp, uu);
           x = ee;
         }
       }
@@ -833,6 +883,10 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
   const bool bf_state = b.state_dt == DType::BF16;
   AKKA_CHECK(!(bf_state && nt), "count_optim: no nontemporal variant with bfloat16 state");
   AKKA_CHECK(!(groups && nt), "count_optim: no nontemporal variant with parameter groups");
+  const bool bf_param = b.param_dt == DType::BF16;
+  AKKA_CHECK(!bf_param || bf_state, "count_optim: bfloat16 parameters need bfloat16 state");
+  AKKA_CHECK(!(bf_param && b.shadow), "count_optim: no shadow with bfloat16 parameters (they are the bf16 weights)");
+  AKKA_CHECK(!(bf_param && nt), "count_optim: no nontemporal variant with bfloat16 parameters");
   AKKA_CHECK(!lamb || (groups && groups->trust), "count_optim: LAMB needs groups, one segment per layer, with a "
                                                  "trust table");
   // bf16 state reads the step for its rounding key, whatever the kind
@@ -848,17 +902,24 @@ void launch_count_optim(hipStream_t s, const OptimBuffers& b, const CountsTable&
   with_elem(b.src_dt, [&](auto ts) {
     with_kind(o.kind, [&](auto kd) {
       with_flag(b.shadow != nullptr, [&](auto sh) {
-        auto launch = [&](auto tm, auto ntv, auto tail) {
+        auto launch_p = [&](auto tp, auto tm, auto ntv, auto tail) {
           using TS = typename decltype(ts)::type;
           using TM = typename decltype(tm)::type;
+          using TP = typename decltype(tp)::type;
           constexpr int KIND = decltype(kd)::value;
-          // LAMB takes its own tail, the other kinds theirs: the mixed instantiations do not exist
-          if constexpr ((KIND == kLamb) == std::is_same_v<decltype(tail), LambTail>)
-            hipLaunchKernelGGL((count_optim_kernel<TS, TM, KIND, decltype(sh)::value, decltype(ntv)::value,
-                                                   decltype(tail)>),
-                               dim3(rg.grid, rg.split), dim3(kBlock), 0, s, b.p, static_cast<TM*>(b.m),
-                               static_cast<TM*>(b.v), static_cast<bf16_t*>(b.shadow), static_cast<const TS*>(b.src),
-                               ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, b.guard, tail);
+          constexpr bool SH = decltype(sh)::value, NTV = decltype(ntv)::value;
+          // LAMB takes its own tail, the other kinds theirs: the mixed instantiations do not exist; nor do those
+          // of bf16 parameters with fp32 moments, a shadow or nontemporal accesses (refused above)
+          constexpr bool param_ok = std::is_same_v<TP, float> || (std::is_same_v<TM, bf16_t> && !SH && !NTV);
+          if constexpr ((KIND == kLamb) == std::is_same_v<decltype(tail), LambTail> && param_ok)
+            hipLaunchKernelGGL((count_optim_kernel<TS, TM, TP, KIND, SH, NTV, decltype(tail)>),
+                               dim3(rg.grid, rg.split), dim3(kBlock), 0, s, static_cast<TP*>(b.p),
+                               static_cast<TM*>(b.m), static_cast<TM*>(b.v), static_cast<bf16_t*>(b.shadow),
+                               static_cast<const TS*>(b.src), ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t,
+                               b.sq, b.guard, tail);
+        };
+        auto launch = [&](auto tm, auto ntv, auto tail) {
+          with_elem(b.param_dt, [&](auto tp) { launch_p(tp, tm, ntv, tail); });
         };
         // nontemporal accesses: fp32 state without groups only (checked above)
         if (nt) return launch(Elem<float>{}, std::true_type{}, PlainTail{b.seed});
@@ -908,6 +969,8 @@ void launch_lamb_norms(hipStream_t s, const OptimBuffers& b, const CountsTable& 
   if (ct.S <= 0) return;
   AKKA_CHECK(b.p && b.m && b.v && b.t && b.src && ct.counts && part, "lamb_norms: null buffer");
   AKKA_CHECK(!b.guard || b.sq, "lamb_norms: a guard needs the norm pass's sq");
+  AKKA_CHECK(b.param_dt != DType::BF16 || b.state_dt == DType::BF16,
+             "lamb_norms: bfloat16 parameters need bfloat16 state");
   AKKA_CHECK(aligned16(b.p) && aligned16(b.m) && aligned16(b.v) && aligned16(b.src) &&
                  (reinterpret_cast<uintptr_t>(part) & 7) == 0,
              "lamb_norms: buffers must be 16-B aligned, the partials 8-B");
@@ -925,13 +988,19 @@ void launch_lamb_norms(hipStream_t s, const OptimBuffers& b, const CountsTable& 
   const OptimK k = host_scalars(o);
   with_elem(b.src_dt, [&](auto ts) {
     with_elem(b.state_dt, [&](auto tm) {
-      using TS = typename decltype(ts)::type;
-      using TM = typename decltype(tm)::type;
-      hipLaunchKernelGGL((lamb_norms_kernel<TS, TM>), dim3(int(g)), dim3(kBlock), 0, s,
-                         reinterpret_cast<float2*>(part), b.p, static_cast<const TM*>(b.m),
-                         static_cast<const TM*>(b.v), static_cast<const TS*>(b.src), ct.counts, ct.S, ct.step, ct.N,
-                         ct.C, ct.kmax, k, b.t, b.sq, b.guard, groups.seg_end, groups.seg_group,
-                         reinterpret_cast<const float4*>(groups.rows), groups.nseg, groups.ngroups);
+      with_elem(b.param_dt, [&](auto tp) {
+        using TS = typename decltype(ts)::type;
+        using TM = typename decltype(tm)::type;
+        using TP = typename decltype(tp)::type;
+        // bf16 parameters with fp32 moments: refused above, not instantiated
+        if constexpr (std::is_same_v<TP, float> || std::is_same_v<TM, bf16_t>)
+          hipLaunchKernelGGL((lamb_norms_kernel<TS, TM, TP>), dim3(int(g)), dim3(kBlock), 0, s,
+                             reinterpret_cast<float2*>(part), static_cast<const TP*>(b.p),
+                             static_cast<const TM*>(b.m), static_cast<const TM*>(b.v), static_cast<const TS*>(b.src),
+                             ct.counts, ct.S, ct.step, ct.N, ct.C, ct.kmax, k, b.t, b.sq, b.guard, groups.seg_end,
+                             groups.seg_group, reinterpret_cast<const float4*>(groups.rows), groups.nseg,
+                             groups.ngroups);
+      });
     });
   });
   check_launch("lamb_norms");

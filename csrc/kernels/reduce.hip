@@ -88,7 +88,10 @@ __global__ __launch_bounds__(kBlock) void reduce_vec_kernel(SrcTable srcs, v4u* 
       if (i < nvec) {
         v4u o;
         if constexpr (NSRC == 1) {
-          o = v[u][0];  // one contributor: the sum is the value itself, bit for bit (-0.0, NaN payloads)
+          // one contributor: this body copies the vector, bit for bit (-0.0, NaN payloads).  The peeled head, the
+          // scalar rest and the Lds kernel have no such case and add the source to +0.0 like any other count: the
+          // same value, a NaN for a NaN, but -0.0 comes out as +0.0 and a payload is the adder's business
+          o = v[u][0];
         } else {
           float acc[E];
 #pragma unroll

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from akka_allreduce_amd.data import AllReduceOutput, OptimGroups, guard_state, lamb_workspace, sqnorm_workspace
+import loop_cases as L
 from lamb_cases import lamb_rule
 from optim_cases import (BF, H_SENTINEL, M_SENTINEL, NGRAD, V_SENTINEL, _bits, _dev, _inputs, _kernel_state,
                          _same_bits, _sr, _step)
@@ -46,6 +47,11 @@ LAYOUTS = {
                 (349999, 0), (400003, 2)],
 }
 ZERO = {1: None, 7: None, 1003: 4, 300_001: 6, 1_000_003: 9}
+# loop_cases.DEEP, where every thread runs the update's two-unit loop: the layers end at loop_cases.DEEP_CUTS (three
+# of them cut one region's body into pieces that each run that loop), groups round-robin, so every third layer has
+# opted out; no layer is zeroed
+LAYOUTS[L.DEEP[0]] = [(e - s, i % 3) for i, (s, e) in enumerate(zip((0,) + L.DEEP_CUTS[:-1], L.DEEP_CUTS))]
+ZERO[L.DEEP[0]] = None
 MISSING_LAYER = {1: None, 7: 0, 1003: 0, 300_001: 2, 1_000_003: 1}
 OPTED_OUT = {1: None, 7: 1, 1003: 6, 300_001: 5, 1_000_003: 6}
 
@@ -255,6 +261,18 @@ def test_trust_ratios_match_float64_and_are_deterministic(S, N, C, src, clip):
 @pytest.mark.parametrize("src", ["fp32", "bf16"])
 @pytest.mark.parametrize("S,N,C", SHAPES)
 def test_update_matches_the_rule(shadow, clip, src, S, N, C):
+    _check_update_matches_the_rule(shadow, clip, src, S, N, C)
+
+
+@pytest.mark.parametrize("clip,shadow", [(False, False), (True, True)])
+@pytest.mark.parametrize("src", ["fp32", "bf16"])
+def test_update_matches_the_rule_in_the_pipelined_loop(src, clip, shadow):
+    L.require_deep()
+    L.require_deep_cuts()
+    _check_update_matches_the_rule(shadow, clip, src, *L.DEEP)
+
+
+def _check_update_matches_the_rule(shadow, clip, src, S, N, C):
     inp, lay = _inputs(S, N, C, src), Layout(S)
     ref64, ref32 = _references(S, N, C, src, clip)
     missing = inp["missing"]

@@ -16,17 +16,23 @@ import math
 import pytest
 import torch
 
+import loop_cases as L
 from akka_allreduce_amd.data import AllReduceOutput, sqnorm_workspace
 from optim_cases import (H_SENTINEL, HYPER, M_SENTINEL, NGRAD, V_SENTINEL, _dev, _inputs, _kernel_state, _mlp_run,
                          _step)
 
 pytestmark = pytest.mark.gpu
 
-# the smallest shapes that reach each path of the region walk: one element; regions shorter than a unit (all head
-# and tail); unaligned regions, no multiple of 4 or 8; few regions, so several workgroups share one (gridDim.y > 1)
-# and run the unrolled loop and its remainder; many regions with bodies, heads and tails
+# the smallest shapes that reach each path of the region walk but the pipelined loop: one element; regions shorter
+# than a unit (all head and tail); unaligned regions, no multiple of 4 or 8; few regions, so several workgroups share
+# one (gridDim.y > 1: 74 of them at (300_001, 2, 150_000), a stride of 18 944 units against the region's 18 750, so
+# every thread takes at most one unit, in the remainder loop); many regions with bodies, heads and tails.  None runs
+# update_range's two-unit loop or wraps the grid (test_loop_cases_cpu.py); AT_DEPTH below does.
 SHAPES = [(1, 1, 1), (7, 3, 2), (1003, 4, 67), (300_001, 2, 150_000), (1_000_003, 4, 4099)]
 STEPS = (1, 20)
+# loop_cases.DEEP: every thread runs the two-unit loop at least twice per region; loop_cases.WRAP: more regions than
+# the grid has workgroups
+AT_DEPTH = {L.DEEP: L.require_deep, L.WRAP: L.require_wrap}
 
 
 def _torch_run(kind, inp, dtype, clip):
@@ -76,6 +82,25 @@ def _references(S, N, C, src, kind, clip):
 @pytest.mark.parametrize("src", ["fp32", "bf16"])
 @pytest.mark.parametrize("S,N,C", SHAPES)
 def test_update_matches_torch(shadow, clip, kind, src, S, N, C):
+    _check_update_matches_torch(shadow, clip, kind, src, S, N, C)
+
+
+# DEEP first, one source dtype after the other, so its inputs are built once each
+@pytest.mark.parametrize("clip,shadow", [(False, False), (True, True)])
+@pytest.mark.parametrize("kind", ["sgd", "nesterov", "adamw"])
+@pytest.mark.parametrize("src", ["fp32", "bf16"])
+def test_update_matches_torch_in_the_pipelined_loop(src, kind, clip, shadow):
+    AT_DEPTH[L.DEEP]()
+    _check_update_matches_torch(shadow, clip, kind, src, *L.DEEP)
+
+
+@pytest.mark.parametrize("kind", ["adamw", "sgd"])
+def test_update_matches_torch_where_the_grid_wraps(kind):
+    AT_DEPTH[L.WRAP]()
+    _check_update_matches_torch(True, True, kind, "fp32", *L.WRAP)
+
+
+def _check_update_matches_torch(shadow, clip, kind, src, S, N, C):
     inp = _inputs(S, N, C, src)
     ref64, ref32 = _references(S, N, C, src, kind, clip)
     missing = inp["missing"]

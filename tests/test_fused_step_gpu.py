@@ -22,6 +22,42 @@ def test_colsum_matches_torch(M, ncol, off):
         torch.testing.assert_close(got, want, rtol=1e-5, atol=1e-4 * max(1.0, M ** 0.5))
     # deterministic: the same input gives bitwise the same sums
     assert torch.equal(colsum(x), colsum(x))
+    # the fenced hand-off (lite=False) carries the same partial rows: the tolerance above, and the same bits
+    for _ in range(2):
+        fenced = colsum(x, lite=False)
+        torch.cuda.synchronize()
+        torch.testing.assert_close(fenced, want, rtol=1e-5, atol=1e-4 * max(1.0, M ** 0.5))
+        assert torch.equal(fenced, got)
+
+
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("splits", [1, 16])
+@pytest.mark.parametrize("M,ncol", [(33, 520), (5, 4096)])
+def test_colsum_with_explicit_row_splits(M, ncol, splits, relu):
+    """The row split given by the caller: one workgroup per column tile, and sixteen, most of whose row ranges
+    are empty (3 rows each of 33; 1 each of 5) -- their partial rows are zeros the combine still adds.  Both
+    hand-offs, with and without the fused ReLU backward."""
+    from akka_allreduce_amd.ops import colsum
+
+    g = torch.Generator(device="cuda").manual_seed(M * 7 + ncol + splits)
+    x = torch.randn(M, ncol, device="cuda", generator=g).to(torch.bfloat16)
+    kw, want = {}, x.float().sum(0)
+    if relu:
+        h = torch.relu(torch.randn(M, ncol, device="cuda", generator=g)).to(torch.bfloat16)
+        want_masked = torch.ops.aten.threshold_backward(x, h, 0)
+        want = want_masked.float().sum(0)
+    got = []
+    for lite in (True, False, True):
+        if relu:
+            masked = torch.full_like(x, 7.0)
+            kw = dict(relu_of=h, masked_out=masked)
+        out = colsum(x, splits=splits, lite=lite, **kw)
+        torch.cuda.synchronize()
+        torch.testing.assert_close(out, want, rtol=1e-5, atol=1e-4 * max(1.0, M ** 0.5))
+        if relu:
+            assert torch.equal(masked, want_masked)
+        got.append(out)
+    assert torch.equal(got[0], got[1]) and torch.equal(got[0], got[2])  # the tickets re-arm on either path
 
 
 def test_count_mean_shadow_is_bf16_of_updated_params():
@@ -74,10 +110,12 @@ def test_mlp_bf16_shadow_weights_match_casts():
     assert torch.equal(b.sflat, b.pflat.to(torch.bfloat16))
 
 
-@pytest.mark.parametrize("B,C", [(256, 1000), (7, 3), (33, 4099), (1, 1)])
+# (257, 5) and (1000, 33): the last workgroup's combine loop over the rows (256 per trip) takes two and four trips
+@pytest.mark.parametrize("B,C", [(256, 1000), (7, 3), (33, 4099), (1, 1), (257, 5), (1000, 33)])
 def test_fused_cross_entropy_matches_torch(B, C):
     """Loss and bf16 logit gradient against torch's fp32 cross entropy of the
-    same bf16 logits, with a few ignored labels and a non-unit upstream grad."""
+    same bf16 logits, with a few ignored labels and a non-unit upstream grad;
+    both the same bits on every call."""
     import torch.nn.functional as F
 
     from akka_allreduce_amd.ops import cross_entropy
@@ -88,6 +126,7 @@ def test_fused_cross_entropy_matches_torch(B, C):
     if B > 4:
         y[1] = -100  # ignored rows: excluded from the mean
         y[3] = -100
+    calls = []
     for _ in range(2):  # the ticket re-arms
         a = logits.clone().requires_grad_(True)
         loss = cross_entropy(a, y)
@@ -98,6 +137,30 @@ def test_fused_cross_entropy_matches_torch(B, C):
         torch.testing.assert_close(loss, want, rtol=1e-5, atol=1e-5)
         assert a.grad.dtype == torch.bfloat16
         torch.testing.assert_close(a.grad.float(), r.grad, rtol=1e-2, atol=2e-3 * float(r.grad.abs().max()) + 1e-6)
+        calls.append((loss.detach().clone(), a.grad.clone()))
+    # the combine sums the rows in a fixed order: the same bits, not merely close
+    assert torch.equal(calls[0][0], calls[1][0]) and torch.equal(calls[0][1], calls[1][1])
+
+
+def test_fused_cross_entropy_of_a_batch_with_every_label_ignored():
+    """Every label -100: the loss is NaN as torch's, the gradient all zeros, and the next call on the same
+    workspace is finite again -- the last arriver re-armed the ticket on that path too."""
+    import torch.nn.functional as F
+
+    from akka_allreduce_amd.ops import cross_entropy
+
+    B, C = 257, 5
+    g = torch.Generator(device="cuda").manual_seed(B)
+    logits = (4 * torch.randn(B, C, device="cuda", generator=g)).to(torch.bfloat16)
+    ignored = torch.full((B,), -100, device="cuda")
+    a = logits.clone().requires_grad_(True)
+    loss = cross_entropy(a, ignored)
+    loss.backward()
+    assert torch.isnan(loss).item() and torch.isnan(F.cross_entropy(logits.float(), ignored)).item()
+    assert a.grad.dtype == torch.bfloat16 and bool((a.grad == 0).all())
+    y = torch.randint(0, C, (B,), device="cuda", generator=g)
+    again = cross_entropy(logits, y)
+    torch.testing.assert_close(again, F.cross_entropy(logits.float(), y), rtol=1e-5, atol=1e-5)
 
 
 def test_fused_cross_entropy_flags_invalid_labels():
@@ -226,3 +289,8 @@ def test_colsum_fused_relu_backward_matches_torch(M, ncol, off):
     torch.cuda.synchronize()
     assert torch.equal(masked, want_masked)
     torch.testing.assert_close(got, want_masked.float().sum(0), rtol=1e-5, atol=1e-4 * max(1.0, M ** 0.5))
+    # the fenced hand-off: the same mask, the same sums bit for bit
+    masked2 = torch.empty(M, ncol, device="cuda", dtype=torch.bfloat16)
+    fenced = colsum(dy, relu_of=h, masked_out=masked2, lite=False)
+    torch.cuda.synchronize()
+    assert torch.equal(masked2, want_masked) and torch.equal(fenced, got)
